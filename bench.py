@@ -8,6 +8,11 @@ at BASELINE.json configs[1]: 30 slots, 64x64x3, 1 seed + 19 predicted frames.  I
 are resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-extra]
+                    [--dump-outputs DIR]
+
+--dump-outputs DIR: after the K timed steps of the reported value, rank 0 writes what the LAST of them computed -- every
+tensor forward_eval returns, and the PSNR / SSIM rows of the metric step -- as DIR/<name>.npy (dump_outputs: at most
+64 MB in all).  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU.  Under torchrun (WORLD_SIZE set) this process IS one rank; otherwise
 ``--gpus N`` makes this process a launcher that starts N fresh worker processes (RANK / LOCAL_RANK /
@@ -41,6 +46,7 @@ import statistics
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -83,7 +89,12 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the batch-32 / 8 / 1 lines, the per-kernel pass and the "
                                                            "config-4 / training legs")
     ap.add_argument("--no-legs", action="store_true", help="skip only the config-4 and training legs of `extra`")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def log(msg):
@@ -231,6 +242,36 @@ def run_timed(step, inp, warmup, steps, fence, gather, reduce_max, before=None, 
     elapsed = time.perf_counter() - t0
     extra = after() if after is not None else None
     return reduce_max(elapsed), extra, gathered
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """
+    Write every tensor of ``arrays`` (name -> tensor) as ``out_dir/<name>.npy``, float64 kept and everything else as
+    float32.  Each array gets an equal share of ``budget`` bytes: one that fits is written whole in its own shape, a
+    larger one as the 1-D sample of its flattened values at sorted indices drawn without replacement from a PCG64 stream
+    seeded by the array's name -- the same elements on every run with the same shapes.  Returns {name: shape written}.
+    """
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 256          # 256: room for the .npy header
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        flat = flat if flat.dtype == torch.float64 else flat.float()
+        cap = share // flat.element_size()
+        if flat.numel() > cap:
+            rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence(zlib.crc32(name.encode()))))
+            idx = np.sort(rng.choice(flat.numel(), cap, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            a = flat.reshape(t.shape).cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = a.shape
+    return written
 
 
 def stub_main(args):
@@ -519,6 +560,8 @@ def main():
         tokens, lengths = synth.synth_captions(B, max_len=caption_len, seed=100 + rank)
         return videos, tokens.to(dev), lengths.to(dev), synth.synth_noise(B, NUM_SLOTS, 128, seed=200 + rank).to(dev)
 
+    last = {} if args.dump_outputs else None          # --dump-outputs: what the latest step computed
+
     def step(inp, **kw):
         """ the hot path + the metric step after it: fused clamp + PSNR + SSIM kernel (tocvp_psnr_ssim_f32) """
         videos, tokens, lengths, noise = inp
@@ -527,6 +570,8 @@ def main():
         B, P, C, H, W = out["pred_imgs"].shape
         psnr, ssim = kernels.psnr_ssim(out["pred_imgs"].reshape(B * P, C, H, W),
                                        out["targets"].reshape(B * P, C, H, W), clamp01=True)
+        if last is not None:
+            last.update({k: v for k, v in out.items() if torch.is_tensor(v)}, psnr=psnr.view(B, P), ssim=ssim.view(B, P))
         return torch.stack([psnr.view(B, P), ssim.view(B, P)], dim=-1)        # (B, P, 2)
 
     def fence():
@@ -573,6 +618,11 @@ def main():
     # region 2 (value_no_overlap + the dominant kernel's roofline): the same K steps, serial order, HIP events
     # around the decoder convolutions only -- a kernel's duration is its own when nothing shares the chip.
     elapsed, _, all_metrics = timed(inp, args.warmup, args.steps, timer_only=(), overlap_decode=True)
+    if last is not None:
+        if rank == 0:
+            shapes = dump_outputs(args.dump_outputs, last)
+            log(f"outputs of the last timed step -> {args.dump_outputs}: {shapes}")
+        last = None
     clock = ClockSampler(getattr(torch.cuda.get_device_properties(dev), "pci_bus_id", None)) if rank == 0 else None
     if clock is not None:
         clock.start()

@@ -167,3 +167,28 @@ def test_bench_launcher_end_to_end_with_eight_stub_ranks():
     # RCCL backend with fewer visible devices than ranks (this container has none): refuse, start nothing
     res = _run_launcher({"TOCVP_BENCH_STUB": "1"}, "--gpus", "8", "--batch", "1", "--steps", "1")
     assert res.returncode == 2 and "GPU(s) are visible" in res.stderr and not res.stdout.strip()
+
+
+def test_bench_dump_outputs_is_bounded_seeded_and_float(tmp_path):
+    """ bench.dump_outputs (--dump-outputs): one float32 / float64 .npy per name, arrays within their share of the budget
+    whole and in their shape, larger ones as a sample of their values that is the same on every call, and never more
+    than the budget on disk """
+    import numpy as np
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    arrays = {"big": torch.rand(1000, 300, generator=g), "small": torch.rand(4, 5, generator=g).half(),
+              "wide": torch.rand(50, 50, generator=g, dtype=torch.float64)}
+    budget = 3 * 64 * 1024
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "small.npy", "wide.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], arrays["small"].float().numpy())
+    assert got["wide"].dtype == np.float64 and np.array_equal(got["wide"], arrays["wide"].numpy())
+    big = got["big"]
+    assert big.dtype == np.float32 and big.ndim == 1 and shapes["big"] == big.shape
+    assert 0 < big.size < 300000 and big.nbytes <= budget // 3
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    assert np.isin(big, arrays["big"].numpy()).all()

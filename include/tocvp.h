@@ -648,7 +648,10 @@ int tocvp_sqnorm_partial_f32(const float* x, float* partial, int nblocks, long n
  *  tocvp_conv3x3_t4_f32: dx (n,H,W,C) = relu'(act) * conv_transpose3x3(dy (n,H,W,4), w (4,C,3,3));
  *  tocvp_dec_class_reduce_f32: dS (n,25,64) = per-border-class sums of g (n,H,W,64) * (cpos + S > 0)
  *    (collapsed decoder layer 0, see tocvp_dec_tapsum_f32).
- * The 5x5 data gradients in between reuse tocvp_conv5x5_bf16x3_f32 with transposed, flipped weights. */
+ * The 5x5 data gradients in between reuse the forward convs with transposed, flipped weights:
+ * tocvp_conv5x5_dec_wino_f16x3_f32 with in_amax (operand scale from tocvp_absmax_f32 over the chunk) and gate by
+ * default, tocvp_conv5x5_bf16x3_f32 with gate when the Winograd data gradient is off (TOCVP_TRAIN_WINO_DGRAD=0) or
+ * the decoder runs bf16x3. */
 int tocvp_dec_tail_grad_f32(const float* dimg, const float* recons, const float* masks, float* dy, int F,
                             int K, int H, int W, void* stream);
 int tocvp_conv3x3_t4_f32(const float* dy, const float* w, const float* act, float* dx, int nimg, int H,

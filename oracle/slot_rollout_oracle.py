@@ -92,7 +92,7 @@ def build_grid(resolution):
 def soft_pos_embed(proj_w, proj_b, resolution):
     """ models/Blocks/model_blocks.py:186-226: Conv1x1(grid) as an (H, W, C) addend. """
     grid = build_grid(resolution)[0]                               # (H, W, 4)
-    return grid @ proj_w.reshape(proj_w.shape[0], 4).t() + proj_b  # (H, W, C)
+    return grid.to(proj_w.dtype) @ proj_w.reshape(proj_w.shape[0], 4).t() + proj_b  # (H, W, C)
 
 
 def savi_encode(sd, imgs):

@@ -435,6 +435,48 @@ def test_training_step_gradients_with_image_loss_match_oracle_autograd():
     ts.loss_and_grads(videos.to(DEV), tokens.to(DEV), lengths.to(DEV), init_noise=noise.to(DEV))
 
 
+def test_training_step_gradients_with_image_loss_alone_match_oracle_autograd():
+    """ loss_weights = (1, 0): the predictor gradients come from the image MSE alone, back through the frozen SAVi
+    decoder, so the slot-loss term cannot mask an error of the decoder backward """
+    from oracle import slot_rollout_oracle as O
+    from textocvp_amd.setup_model import default_exp_params, setup_model, setup_predictor
+    from textocvp_amd.train.step import PredictorTrainStep
+    Ks, P, B = 7, 2, 2
+    exp = default_exp_params(num_slots=Ks, num_context=1, num_preds=P)
+    savi, pred = setup_model(exp["model"]).eval(), setup_predictor(exp)
+    synth.fill_module_(savi, prefix="savi.")
+    synth.fill_module_(pred, prefix="pred.")
+    videos = synth.synth_videos(B, 1 + P, seed=0)
+    tokens, lengths = synth.synth_captions(B, max_len=12, lengths=[9, 12], seed=0)
+    noise = synth.synth_noise(B, Ks, 128, seed=1)
+
+    savi_sd = {k: v.detach() for k, v in savi.state_dict().items()}
+    sd = {k: v.detach().clone().requires_grad_(v.dtype.is_floating_point)
+          for k, v in pred.state_dict().items()}
+    with torch.no_grad():
+        hist = O.savi_decomp(savi_sd, videos, noise, 1 + P)
+    preds = O.rollout(sd, hist, tokens, lengths, 1, P)
+    imgs, _, _ = O.savi_decode(savi_sd, preds.reshape(B * P, Ks, 128), (64, 64), 3)
+    l_img = F.mse_loss(imgs.view(B, P, 3, 64, 64), videos[:, 1:1 + P])
+    l_img.backward()
+
+    savi, pred = savi.to(DEV), pred.to(DEV)
+    ts = PredictorTrainStep(savi, pred, lr=1e-4, clip=0.05, warmup_steps=0, text_dropout=0.0, loss_weights=(1.0, 0.0))
+    losses = ts.loss_and_grads(videos.to(DEV), tokens.to(DEV), lengths.to(DEV), init_noise=noise.to(DEV))
+    assert abs(losses["pred_img_mse"] - l_img.item()) < 2e-4 * abs(l_img.item())
+    worst = 0.0
+    for name, var in ts.model.names.items():
+        ref = sd[name].grad
+        if ref is None:
+            assert var.grad is None or var.grad.abs().max().item() == 0.0, name
+            continue
+        e = rel_err(var.grad, ref)
+        worst = max(worst, e)
+        assert e < 5e-3, (name, e)
+    print(f"training step (image loss alone): worst relative gradient error {worst:.2e}; "
+          f"loss img {losses['pred_img_mse']:.5f}")
+
+
 def _build_step(Ks=7, P=2):
     from textocvp_amd.setup_model import default_exp_params, setup_model, setup_predictor
     from textocvp_amd.train.step import PredictorTrainStep

@@ -7,8 +7,11 @@ every chunk of frames is decoded, differentiated and dropped before the next one
 
   slots --(tap-sum GEMM)--> S --relu(cpos + S[cls])--> conv1+relu --> conv2+relu --> conv3+relu
         --> 3x3 tail --> softmax over slots / compositing --> img --> sum (img - target)^2
-Data gradients of the 5x5 convs = the same conv kernels with transposed, flipped weights (bf16x3: the
-bf16 planes keep the fp32 exponent range, which matters for small gradients).
+Data gradients of the 5x5 convs = the same conv operators with transposed, flipped weights: by default the Winograd
+kernel with an operand scale measured on the device per chunk (f16x3 decoder with conv_wino), else the direct bf16x3
+kernel (its bf16 planes keep the fp32 exponent range per element).  The backward weights are derived from the live conv
+weights through the decoder's Derived cache, so they follow load_state_dict, .to() and in-place updates as the forward
+weights do.
 """
 
 import os
@@ -21,7 +24,15 @@ from . import autograd as ag
 __all__ = ["DecoderLoss"]
 
 _L = K.lib
-# 0: data gradients of the decoder convs on the direct bf16x3 kernel (rounds 2-4) instead of the Winograd form
+# 0: data gradients of the decoder convs on the direct bf16x3 kernel (rounds 2-4) instead of the Winograd form.
+# Error model of the Winograd data gradient: one operand scale per chunk and layer, the power of two that maps max |g|
+# over the whole chunk to ~4096; the fp16 planes then hold an element to fp32-class precision down to ~2^-15 of that
+# maximum, coarser below (the matrix core flushes fp16 values under 2^-14), and nothing below ~2^-26 of it.  A slot
+# image whose gradient is small shares the scale of the largest image in its chunk, so its own relative precision
+# drops once it is below ~2^-15 of that image.  Measured against fp64 autograd (tests/test_decoder_backward_gpu.py,
+# 30 saturated slots, error relative to each image's own maximum): 1.1e-4 or better down to 2^-20 of the chunk maximum
+# (the same as with the bf16x3 data gradient), 5e-3 between 2^-20 and 2^-30 (bf16x3: 4e-5), 3e-2 below (bf16x3: 1e-5);
+# relative to a frame's maximum, 2.4e-6 at worst.
 _WINO_DGRAD = os.environ.get("TOCVP_TRAIN_WINO_DGRAD", "1") != "0"
 
 
@@ -36,19 +47,24 @@ class DecoderLoss:
             raise NotImplementedError("training step: SAVi ConvDecoder with 4 conv blocks (reference config)")
         self.savi, self.dec = savi, dec
         self.frames_per_chunk = frames_per_chunk
-        self._bwd_w = None
 
-    def _backward_weights(self):
-        """ W'[ci][co][dy][dx] = W[co][ci][4-dy][4-dx] of conv blocks 1..3, split for the bf16x3 kernel """
-        if self._bwd_w is None:
-            out = {}
-            for i in (1, 2, 3):
-                w = self.dec.decoder[i].conv.weight.detach()
-                wt = w.flip(-1, -2).transpose(0, 1).contiguous()
-                out[i] = (K.split_conv_weights_bf16(wt), K.split_conv_weights_frag_bf16(wt))
-            self._bwd_w = out
-            self._zero_bias = torch.zeros(64, device=w.device, dtype=torch.float32)
-        return self._bwd_w
+    # The backward weights live in the decoder's Derived cache like its forward weights: they are rebuilt when a
+    # conv weight is replaced, moved or modified in place (load_state_dict, .to(device), an update under no_grad).
+    def _transposed(self, i):
+        """ W'[ci][co][dy][dx] = W[co][ci][4-dy][4-dx] of conv block i """
+        return self.dec.decoder[i].conv.weight.detach().flip(-1, -2).transpose(0, 1).contiguous()
+
+    def _backward_weights(self, i):
+        """ the transposed, flipped weights of conv block i split for the bf16x3 kernel (planes, fragments) """
+        def build():
+            wt = self._transposed(i)
+            return K.split_conv_weights_bf16(wt), K.split_conv_weights_frag_bf16(wt)
+        return self.dec._derived.get(f"bwd_bf16x3_{i}", [self.dec.decoder[i].conv.weight], build)
+
+    def _zero_bias(self):
+        w = self.dec.decoder[1].conv.weight
+        return self.dec._derived.get("bwd_zero_bias", [w],
+                                     lambda: torch.zeros(64, device=w.device, dtype=torch.float32))
 
     def _conv_fwd(self, i, x, collapsed=None):
         conv = self.dec.decoder[i].conv
@@ -61,16 +77,10 @@ class DecoderLoss:
         return K.conv5x5_bf16x3(x, self.dec._split(i), conv.bias, relu=True, collapsed=collapsed,
                                 wfrag=self.dec._split_frag(i))
 
-    def _backward_weights_wino(self):
-        """ the same transposed, flipped weights as Winograd weight images (split-fp16 planes, per-row scales) """
-        if getattr(self, "_bwd_wino", None) is None:
-            out = {}
-            for i in (1, 2, 3):
-                w = self.dec.decoder[i].conv.weight.detach()
-                out[i] = K.split_conv_weights_wino_f16x3(w.flip(-1, -2).transpose(0, 1).contiguous())
-            self._bwd_wino = out
-            self._zero_bias = torch.zeros(64, device=w.device, dtype=torch.float32)
-        return self._bwd_wino
+    def _backward_weights_wino(self, i):
+        """ the same transposed, flipped weights as a Winograd weight image (split-fp16 planes, per-row scales) """
+        return self.dec._derived.get(f"bwd_wino_{i}", [self.dec.decoder[i].conv.weight],
+                                     lambda: K.split_conv_weights_wino_f16x3(self._transposed(i)))
 
     def _conv_bwd(self, i, g, gate=None):
         """ data gradient of conv block i; ``gate`` = the block's input activation (post-ReLU): the gradient
@@ -78,10 +88,11 @@ class DecoderLoss:
         if self.dec.conv_precision == "f16x3" and self.dec.conv_wino and _WINO_DGRAD:
             # the Winograd form of the same operator (2.5 x fewer matrix products, ~2^-21 per product instead of the
             # bf16 planes' ~2^-16); the gradient's magnitude is measured on the device and sets the operand scale
-            wp = self._backward_weights_wino()[i]
-            return K.conv5x5_dec_wino(g, wp, self._zero_bias, relu=False, in_mode=2, out_mode=0, auto_scale=True, gate=gate)
-        ws, wf = self._backward_weights()[i]
-        return K.conv5x5_bf16x3(g, ws, self._zero_bias, relu=False, wfrag=wf, gate=gate)
+            wp = self._backward_weights_wino(i)
+            return K.conv5x5_dec_wino(g, wp, self._zero_bias(), relu=False, in_mode=2, out_mode=0, auto_scale=True,
+                                      gate=gate)
+        ws, wf = self._backward_weights(i)
+        return K.conv5x5_bf16x3(g, ws, self._zero_bias(), relu=False, wfrag=wf, gate=gate)
 
     @torch.no_grad()
     def loss_and_slot_grad(self, slots, targets, grad_scale):

@@ -692,6 +692,47 @@ def train_fixtures(out_dir):
     print("train_c5: losses", l_img.item(), l_slot.item(), "params", len(names), "kept", sorted(full))
 
 
+def train_k30_fixtures(out_dir):
+    """
+    The recipe of train_fixtures at a shape whose linears reach the split-K weight-gradient kernels of the training
+    step: K=30, B=8, 1 seed + 12 preds, input buffer 10 (the window slides for the last two steps), so a rollout step
+    of window w feeds 240 w token rows to the full-window linears.  Stored: the two losses, the L2 norm of every
+    parameter gradient and six gradients (every 4th row / column of the large matrices).
+    """
+    B, Ks, P = 8, 30, 12
+    savi, wrapper = build_reference(num_slots=Ks, num_context=1, num_preds=P, buffer_size=10)
+    wrapper.eval()
+    for p_ in savi.parameters():
+        p_.requires_grad_(False)
+    videos = synth.synth_videos(B, 1 + P, seed=0)
+    tokens, lengths = synth.synth_captions(B, max_len=12, seed=0)
+    noise = synth.synth_noise(B, Ks, 128, seed=1)
+    C, H, W = videos.shape[2:]
+    with torch.no_grad(), FixedNoise(noise):
+        hist = savi(mode="decomp", x=videos, num_imgs=1 + P, decode=False,
+                    caption_tokens=tokens, caption_lengths=lengths)["slot_history"]
+    pred_slots = wrapper(hist, caption_tokens=tokens, caption_lengths=lengths)
+    dec = savi(mode="decode", slots=pred_slots.clone().reshape(B * P, Ks, 128))
+    pred_imgs = dec["recons_imgs"].view(B, P, C, H, W)
+    mse = torch.nn.MSELoss()
+    l_img = mse(pred_imgs, videos[:, 1:1 + P])
+    l_slot = mse(pred_slots, hist[:, 1:1 + P])
+    (l_img + l_slot).backward()
+    names, norms, full = [], [], {}
+    keep = ("predictor.mlp_in.weight", "predictor.mlp_out.weight", "predictor.predictor.0.mlp.0.weight",
+            "predictor.predictor.0.attn.q.weight", "predictor.pe.pe", "predictor.text_encoder.transformer.layers.0.linear1.weight")
+    for name, p_ in wrapper.named_parameters():
+        g = torch.zeros_like(p_) if p_.grad is None else p_.grad
+        names.append(name)
+        norms.append(float(g.norm()))
+        if name in keep:
+            full["grad::" + name] = (g[::4, ::4] if g.dim() == 2 and g.numel() > 40000 else g).detach().numpy()
+    assert len(full) == len(keep), sorted(full)
+    np.savez(os.path.join(out_dir, "train_k30.npz"), loss_img=l_img.item(), loss_slot=l_slot.item(),
+             names=np.array(names), grad_norms=np.array(norms, dtype=np.float64), **full)
+    print("train_k30: losses", l_img.item(), l_slot.item(), "params", len(names), "kept", sorted(full))
+
+
 @torch.no_grad()
 def manifest(out_dir):
     """ state_dict key/shape manifest = the checkpoint-layout contract. """
@@ -708,7 +749,7 @@ def manifest(out_dir):
 if __name__ == "__main__":
     torch.set_num_threads(8)
     what = sys.argv[1:] or ["manifest", "units", "e2e", "parity", "longcap", "decomp", "uncond", "dinosaur", "t5",
-                            "train", "dinov2", "e2e_c4"]
+                            "train", "train_k30", "dinov2", "e2e_c4"]
     if "manifest" in what:
         manifest(HERE)
     if "units" in what:
@@ -729,6 +770,8 @@ if __name__ == "__main__":
         t5_fixtures(HERE)
     if "train" in what:
         train_fixtures(HERE)
+    if "train_k30" in what:
+        train_k30_fixtures(HERE)
     if "dinov2" in what:
         dinov2_fixtures(HERE)
     if "e2e_c4" in what:

@@ -658,6 +658,26 @@ int tocvp_conv3x3_t4_f32(const float* dy, const float* w, const float* act, floa
                          int W, int C, void* stream);
 int tocvp_dec_class_reduce_f32(const float* g, const float* cpos, const float* S, float* dS, int nimg,
                                int H, int W, int C, void* stream);
+/* Frozen ExtendedDINOSAUR MLPPatchDecoder, backward w.r.t. the slots (image-loss term; decoders.py:264-365
+ * differentiated):
+ *  tocvp_conv3x3_dgrad_bf16x3_f32: dx (nimg,H,W,Cout) = gate' * data gradient of a 3x3 conv (pad 1) over g
+ *    (nimg,H,W,Cg), or with up2 of "nearest x2 -> 3x3 conv" over g (nimg,2H,2W,Cg) (16 taps of a stride-2 4x4 conv,
+ *    the adjoint of tocvp_conv3x3_up2_f16x3_f32).  w (9 or 16 taps, Cout, Cg) fp32; gate (nimg,H,W,Cout) may be NULL
+ *    (else dx = 0 where gate <= 0).  bf16x3 split operands (fp32 exponent range).  Cg % 32 == 0, Cout % 64 == 0.
+ *  tocvp_bilinear_resize_bwd_f32: adjoint of tocvp_bilinear_resize_f32 in gather form: dy NCHW (n,C,OH,OW) ->
+ *    dx NHWC (n,SH,SW,cstride), channels [C, cstride) zero.
+ *  tocvp_slot_composite_bwd_f32: adjoint of tocvp_slot_composite_f32: dR (B,N,F), decoded (B,K,N,ld), masks
+ *    (B,K,N) -> ddec (B,K,N,ld) = alpha dR in [0,F), alpha (<feat,dR> - sum_j alpha_j <feat_j,dR>) at F, 0 beyond.
+ *  tocvp_ln_bcast_bwd_f32: dslot (S,D) = sum over n of the LayerNorm backward of dy (S,N,D) at x = slot[s] + pos[n]
+ *    (D in {64, 128, 256, 512}). */
+int tocvp_conv3x3_dgrad_bf16x3_f32(const float* g, const float* w, const float* gate, float* dx, int nimg, int H,
+                                   int W, int Cg, int Cout, int up2, void* stream);
+int tocvp_bilinear_resize_bwd_f32(const float* dy, float* dx, int n, int C, int cstride, int SH, int SW, int OH,
+                                  int OW, void* stream);
+int tocvp_slot_composite_bwd_f32(const float* dR, const float* decoded, const float* masks, float* ddec, int B,
+                                 int K, int N, int F, int ld, void* stream);
+int tocvp_ln_bcast_bwd_f32(const float* slots, const float* pos, const float* gamma, const float* dy, float* dslot,
+                           int S, int N, int D, float eps, void* stream);
 /* torch.optim.Adam step (no weight decay / amsgrad) on a flat parameter.  The step-dependent scalars are
  * read from DEVICE memory so that a captured HIP graph of the training step can be replayed:
  * hyper = {lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}; gscale (may be NULL) = clipping factor.

@@ -249,6 +249,18 @@ _SIGNATURES = {
     "tocvp_dec_class_reduce_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_conv3x3_dgrad_bf16x3_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_bilinear_resize_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_slot_composite_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_ln_bcast_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_float, ctypes.c_void_p]),
     "tocvp_adam_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tocvp_clip_scale_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
@@ -1713,6 +1725,65 @@ def bilinear_resize_nhwc_to_nchw(x, channels, out_h, out_w):
     _check(lib().tocvp_bilinear_resize_f32(_ptr(x), _ptr(y), n, channels, Cs, SH, SW, out_h, out_w,
                                            _stream()), "tocvp_bilinear_resize_f32")
     return y
+
+
+def conv3x3_dgrad(g, w, out_hw, gate=None, up2=False):
+    """
+    Data gradient of a 3x3 conv (pad 1) -- or of "nearest x2 -> 3x3 conv" (up2) -- over the gradient image
+    g (n, GH, GW, Cg) NHWC -> dx (n, H, W, Cout) with (GH, GW) = (H, W), or (2 H, 2 W) for up2; w (9 or 16 taps,
+    Cout, Cg) from the training step's derived weights (transposed, flipped or phase-summed, BatchNorm scale folded);
+    ``gate`` (n, H, W, Cout): dx is zeroed where gate <= 0 (the ReLU of the layer below).  bf16x3 split operands.
+    """
+    n, GH, GW, Cg = g.shape
+    H, W = out_hw
+    Cout = w.shape[1]
+    assert g.is_contiguous() and w.is_contiguous() and w.shape == ((16 if up2 else 9), Cout, Cg)
+    assert (GH, GW) == ((2 * H, 2 * W) if up2 else (H, W))
+    assert gate is None or (gate.is_contiguous() and tuple(gate.shape) == (n, H, W, Cout))
+    dx = torch.empty((n, H, W, Cout), device=g.device, dtype=torch.float32)
+    _timed(lambda: f"conv3x3_dgrad{'_up2' if up2 else ''}_{n}x{H}x{W}x{Cg}x{Cout}",
+           2.0 * n * H * W * w.shape[0] * Cg * Cout, lambda: _check(
+               lib().tocvp_conv3x3_dgrad_bf16x3_f32(_ptr(g), _ptr(w), _ptr(gate), _ptr(dx), n, H, W, Cg, Cout,
+                                                    int(bool(up2)), _stream()), "tocvp_conv3x3_dgrad_bf16x3_f32"))
+    return dx
+
+
+def bilinear_resize_bwd(dy, src_hw, cstride):
+    """ adjoint of bilinear_resize_nhwc_to_nchw: dy (n, C, OH, OW) -> (n, SH, SW, cstride), zero channels >= C """
+    n, C, OH, OW = dy.shape
+    SH, SW = src_hw
+    assert dy.is_contiguous() and cstride >= C
+    dx = torch.empty((n, SH, SW, cstride), device=dy.device, dtype=torch.float32)
+    _check(lib().tocvp_bilinear_resize_bwd_f32(_ptr(dy), _ptr(dx), n, C, cstride, SH, SW, OH, OW, _stream()),
+           "tocvp_bilinear_resize_bwd_f32")
+    return dx
+
+
+def slot_composite_bwd(drecons, decoded, masks, feat_dim):
+    """
+    adjoint of slot_composite: drecons (B, N, F), decoded (B, K, N, ld), masks (B, K, N) -> ddecoded (B, K, N, ld)
+    (feature columns, the alpha logit at F, zeros in the padding columns)
+    """
+    B, Ks, N, ld = decoded.shape
+    assert drecons.is_contiguous() and decoded.is_contiguous() and masks.is_contiguous()
+    assert tuple(drecons.shape) == (B, N, feat_dim) and masks.numel() == B * Ks * N
+    out = torch.empty_like(decoded)
+    _check(lib().tocvp_slot_composite_bwd_f32(_ptr(drecons), _ptr(decoded), _ptr(masks), _ptr(out), B, Ks, N,
+                                              int(feat_dim), ld, _stream()), "tocvp_slot_composite_bwd_f32")
+    return out
+
+
+def ln_bcast_bwd(slots, pos, gamma, dy, eps):
+    """
+    slots (S, D), pos (N, D), dy (S, N, D) = gradient of LayerNorm(slots[s] + pos[n]) -> dslots (S, D) (sum over n)
+    """
+    S, D = slots.shape
+    N = pos.shape[0]
+    assert slots.is_contiguous() and pos.is_contiguous() and dy.is_contiguous() and dy.numel() == S * N * D
+    out = torch.empty_like(slots)
+    _check(lib().tocvp_ln_bcast_bwd_f32(_ptr(slots), _ptr(pos), _ptr(gamma), _ptr(dy), _ptr(out), S, N, D,
+                                        float(eps), _stream()), "tocvp_ln_bcast_bwd_f32")
+    return out
 
 
 def rms_norm(x, gamma, eps):

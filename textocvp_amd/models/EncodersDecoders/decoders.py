@@ -331,12 +331,13 @@ class MLPPatchDecoder(nn.Module):
     range_fallbacks = {"mlp_precision": {"f16x3": "fp32"}, "conv_precision": {"f16x3": "fp32"}}
 
     # -- image head on the kernels ---------------------------------------------------------------
-    def _render(self, feats):
+    def _render(self, feats, keep=None):
         with K.range_owner(self, "conv_precision"):
-            return self._render_impl(feats)
+            return self._render_impl(feats, keep)
 
-    def _render_impl(self, feats):
-        """ feats (B, N, F) -> images (B, 3, S, S) """
+    def _render_impl(self, feats, keep=None):
+        """ feats (B, N, F) -> images (B, 3, S, S); ``keep`` (a list) receives every block's post-ReLU output and the
+        final conv's (B, S', S', 32) output before the resize (the training step's backward reads them) """
         B = feats.shape[0]
         g = self.patch_grid[0]
         x = feats.reshape(B, g, g, feats.shape[-1]).contiguous()           # NHWC feature grid
@@ -358,6 +359,8 @@ class MLPPatchDecoder(nn.Module):
                 x = K.conv3x3_up2(x, wph, sc, sf, relu=True)
             else:
                 x = K.conv3x3(x, wp, sc, sf, relu=True, upsample2=up_next, precision=self.conv_precision)
+            if keep is not None:
+                keep.append(x)
             up_next = up
         final = self.conv_patch_decoder[-1]
 
@@ -378,6 +381,8 @@ class MLPPatchDecoder(nn.Module):
         else:
             x = K.conv3x3(x, wp, None, bias, relu=False, upsample2=up_next,     # (B, S', S', 32), 3 used
                           precision=self.conv_precision)
+        if keep is not None:
+            keep.append(x)
         S = self.image_size
         return K.bilinear_resize_nhwc_to_nchw(x, 3, S, S)                  # also the NHWC->NCHW step
 

@@ -1,9 +1,10 @@
 """
 One optimisation step of the TextOCVP predictor (reference 04_train_predictor.py:57-108):
 
-  slot_history = SAVi.decomp(videos)                      (frozen, no gradient)
+  slot_history = SAVi.decomp(videos)                      (frozen, no gradient; SAVi or ExtendedDINOSAUR)
   pred_slots   = autoregressive rollout                    (TrainablePredictor, BPTT)
-  pred_imgs    = SAVi.decode(pred_slots)                   (frozen decoder, gradient w.r.t. the slots)
+  pred_imgs    = SAVi.decode(pred_slots)                   (frozen decoder, gradient w.r.t. the slots:
+                                                            DecoderLoss / PatchDecoderLoss)
   loss = w_img * MSE(pred_imgs, target_imgs) + w_slot * MSE(pred_slots, target_slots)   (CONFIG.py:42-51)
   clip_grad_norm_(0.05) -> Adam(lr 1e-4) with linear warm-up + cosine annealing (lib/setup_model.py:285-332)
 
@@ -20,6 +21,7 @@ import torch.distributed as dist
 from .. import kernels as K
 from . import autograd as ag
 from .decoder import DecoderLoss
+from .patch_decoder import PatchDecoderLoss
 from .predictor import TrainablePredictor
 
 __all__ = ["PredictorTrainStep", "StepResult"]
@@ -68,7 +70,11 @@ class PredictorTrainStep:
                  process_group=None, text_dropout=None, generator=None):
         self.savi, self.wrapper = savi.eval(), wrapper
         self.model = TrainablePredictor(wrapper, text_dropout=text_dropout, generator=generator)
-        self.decoder = DecoderLoss(savi)
+        # the frozen model's decoder: SAVi's ConvDecoder or ExtendedDINOSAUR's MLPPatchDecoder
+        if type(savi.decoder).__name__ == "MLPPatchDecoder":
+            self.decoder = PatchDecoderLoss(savi)
+        else:
+            self.decoder = DecoderLoss(savi)
         self.lr, self.betas, self.eps, self.clip = lr, betas, eps, clip
         self.w_img, self.w_slot = loss_weights
         self.warmup_steps, self.scheduler_steps, self.eta_min = warmup_steps, scheduler_steps, eta_min
@@ -146,7 +152,7 @@ class PredictorTrainStep:
                     self.model.precision = "bf16x6"
                 elif "attention" in msg and K._ATTN_QK16:
                     K._ATTN_QK16 = False
-                elif "conv" in msg and self.decoder.dec.conv_precision == "f16x3":
+                elif "conv" in msg and isinstance(self.decoder, DecoderLoss) and self.decoder.dec.conv_precision == "f16x3":
                     self.decoder.dec.conv_precision = "bf16x3"
                 else:
                     raise

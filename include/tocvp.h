@@ -681,7 +681,8 @@ int tocvp_ln_bcast_bwd_f32(const float* slots, const float* pos, const float* ga
 /* torch.optim.Adam step (no weight decay / amsgrad) on a flat parameter.  The step-dependent scalars are
  * read from DEVICE memory so that a captured HIP graph of the training step can be replayed:
  * hyper = {lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}; gscale (may be NULL) = clipping factor.
- * tocvp_clip_scale_f32: out[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) (clip_grad_norm_), out[1] = norm */
+ * tocvp_clip_scale_f32: out[0] = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6)) (clip_grad_norm_; NaN for a NaN norm,
+ * as torch's clamp), out[1] = norm; max_norm <= 0: no clipping, out[0] = 1 */
 int tocvp_adam_f32(float* p, const float* g, float* m, float* v, long n, const float* hyper,
                    const float* gscale, void* stream);
 int tocvp_clip_scale_f32(const float* sumsq, float max_norm, float* out, void* stream);

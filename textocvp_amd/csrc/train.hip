@@ -239,10 +239,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[i] -= (lr / bc1) * (mi / denom);
 }
 
-// clip_grad_norm_: out[0] = min(1, max_norm / (sqrt(sumsq) + 1e-6)), out[1] = sqrt(sumsq)
+// clip_grad_norm_: out[0] = min(1, max_norm / (sqrt(sumsq) + 1e-6)), out[1] = sqrt(sumsq).  A NaN norm gives a
+// NaN factor, as torch's clamp does (fminf would return 1 and leave every finite element updated as usual)
 __global__ void clip_scale_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ out) {
     const float norm = sqrtf(sumsq[0]);
-    out[0] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+    const float c = max_norm / (norm + 1e-6f);
+    out[0] = max_norm > 0.f ? (c < 1.f || c != c ? c : 1.f) : 1.f;
     out[1] = norm;
 }
 

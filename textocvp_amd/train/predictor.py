@@ -76,7 +76,9 @@ class TrainablePredictor:
         for name, p in wrapper.named_parameters():
             if not p.requires_grad:                  # frozen (the T5 encoder): no gradient, no optimiser state
                 continue
-            v = ag.Var(p.data, requires_grad=True, name=name)
+            # p.detach(), not p.data: it shares p's version counter, so load_state_dict or an in-place edit of
+            # the parameter invalidates every cache keyed on the Var's tensor (kernels._split_weight planes)
+            v = ag.Var(p.detach(), requires_grad=True, name=name)
             self.vars[id(p)] = v
             self.names[name] = v
             self.params[name] = p
@@ -84,20 +86,46 @@ class TrainablePredictor:
     def V(self, param):
         return self.vars[id(param)]
 
+    def sync(self):
+        """
+        Re-bind the Vars to parameters the module REPLACED since the last call (load_state_dict(assign=True),
+        ``p.data = ...``): the optimiser and the rollout then work on the tensors the module owns.  Returns the
+        names that were re-bound (any captured graph of the step still holds the old pointers).
+        """
+        moved = []
+        for name, p in self.wrapper.named_parameters():
+            old = self.params.get(name)
+            if old is None:
+                continue
+            v = self.names[name]
+            if old is p and v.data.data_ptr() == p.data_ptr():
+                continue
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.shape == v.data.shape
+                    and p.device == v.data.device):
+                raise TypeError(f"training step: parameter {name!r} was replaced by a {tuple(p.shape)} {p.dtype} "
+                                f"tensor on {p.device}; the step trains contiguous fp32 {tuple(v.data.shape)} "
+                                f"tensors on {v.data.device}")
+            del self.vars[id(old)]
+            v.data = p.detach()
+            self.vars[id(p)] = v
+            self.params[name] = p
+            moved.append(name)
+        return moved
+
     def zero_grad(self):
         for v in self.vars.values():
             v.grad = None
 
     def mark_updated(self):
         """ the optimiser kernel wrote the weights through raw pointers: bump the tensor version counters so
-        that every cache derived from a weight (operand planes, fused / packed copies) is rebuilt """
+        that every cache derived from a weight (operand planes, fused / packed copies) is rebuilt.  The Var's
+        tensor shares its parameter's counter: one bump covers both. """
         bump = getattr(torch._C, "_increment_version", None)
-        for name, p in self.params.items():
-            for t in (p, self.names[name].data):
-                if bump is not None:
-                    bump(t)
-                else:
-                    t.add_(0)
+        for v in self.names.values():
+            if bump is not None:
+                bump(v.data)
+            else:
+                v.data.add_(0)
 
     # ---------------------------------------------------------------------------------------
     def _lin(self, tape, x, mod, act=K.ACT_NONE, residual=None):

@@ -159,8 +159,16 @@ class PredictorTrainStep:
                 warnings.warn(f"training step: {msg} -- switched that arithmetic to its fp32-range fallback")
         raise K.TocvpError("training step: operands out of the fp16-plane range after every fallback")
 
+    def _follow_params(self):
+        """ parameters the module replaced (load_state_dict(assign=True)): the Vars re-bind to them, the next pass
+        is range-checked again and the captured graphs, which hold the old pointers, are dropped """
+        if self.model.sync():
+            self._graphs = None
+            self._range_ok = False
+
     def loss_and_grads(self, videos, caption_tokens, caption_lengths, **others):
         """ forward + backward; leaves the gradients in ``self.model.names[*].grad``; returns the losses """
+        self._follow_params()
         if not getattr(self, "_range_ok", False):
             sq_slot, sc_slot, sq_img, sc_img = self._range_checked_pass(videos, caption_tokens, caption_lengths, others)
             self._range_ok = True
@@ -309,6 +317,7 @@ class PredictorTrainStep:
 
     def apply(self):
         """ clip_grad_norm_ + Adam on every predictor parameter; returns (grad norm, lr used) """
+        self._follow_params()
         lr = self._set_hyper()
         clipn = self._optimizer_kernels()
         self.model.mark_updated()
@@ -331,6 +340,7 @@ class PredictorTrainStep:
         Dropout samples come from torch's graph-safe generator state, so every replay draws new masks.
         Returns a StepResult: the numbers are fetched when first read, not here.
         """
+        self._follow_params()
         if getattr(self, "_graphs", None) is None:
             warm = self.step(videos, caption_tokens, caption_lengths, **others)   # eager step (fills caches)
             self._static = [videos.clone(), None if caption_tokens is None else caption_tokens.clone(),

@@ -434,7 +434,7 @@ int tocvp_dec_tapsum_f32(const float* w, float* out, int Cout, int Cin, void* st
  * split RGB / alpha, softmax over the K slots, recon = sum_K rgb * mask.
  *   x:(F*K,H,W,Cin) NHWC; w:(4,Cin,3,3) nn.Conv2d layout; bias:(4)
  *   recons_imgs:(F,3,H,W)  recons:(F,K,3,H,W)  masks:(F,K,1,H,W)   (reference output layouts)
- *   K <= 32, Cin == 64, H % 16 == 0, W % 16 == 0.
+ *   K <= 32, Cin in {32, 64, 128}, H % 16 == 0, W % 16 == 0.
  *   ws: >= 9*Cin*4*4 bytes of scratch (weights repacked to [tap][c][4] for scalar-path reads).
  * ------------------------------------------------------------------------------------------- */
 int tocvp_dec_tail_f32(const float* x, const float* w, const float* bias, float* recons_imgs,
@@ -530,6 +530,36 @@ int tocvp_conv3x3_up2_f16x3_f32(const float* x, const void* wphase_frag, const f
  * (25, Cout, Cin) weights of tocvp_pack_conv_weights_f32 (see tocvp_conv3x3_f16x3_f32). */
 int tocvp_conv5x5_f16x3_f32(const float* x, const void* wfrag, const float* bias, float* y, int nimg,
                             int H, int W, int Cin, int Cout, int relu, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * SAVi encoder / decoder variants of the reference factory (encoders.py:38-42, decoders.py:28-38, 96-112):
+ * kernel ksize in {3, 5, 7} (pad ksize / 2), nearest x2 upsampling of the input (upsample2), per-channel scale (NULL = 1) /
+ * shift epilogue (conv bias and eval BatchNorm folded, model_blocks.py:92-93) and optional ReLU, NHWC fp32.
+ * Cin, Cout in {32, 64, 128} (TOCVP_EINVAL otherwise).  x (nimg, SH, SW, Cin); y (nimg, H, W, Cout) with H, W = SH, SW or
+ * 2 SH, 2 SW.
+ *  tocvp_convk_f32: fp32 MFMA; wp (ksize^2, Cout, Cin) from tocvp_pack_conv_weights_f32; the upsampling is read through
+ *    the tile loader.  H % 8 == 0.
+ *  tocvp_convk_f16x3_f32: f16x3 split operands (fp32-class, |x| < 255, |w| < 63); SH % 8 == 0.  Without upsampling wfrag =
+ *    tocvp_split_weights_frag_f16 of the (ksize^2, Cout, Cin) packed weights; with upsample2 the conv runs as four phase
+ *    convolutions over the source image, T = ksize / 2 + 1 taps per direction: wfrag of (4 phases = 2 a + b, T^2 taps =
+ *    T i + j, Cout, Cin), tap (i, j) of phase (a, b) reading source pixel (y + floor((a - ksize/2) / 2) + i, x +
+ *    floor((b - ksize/2) / 2) + j) and holding the sum of the ksize x ksize taps that fall on it (kernels.pack_conv_up2_weights).
+ *  tocvp_convk_in3_f32: first encoder layer, 3 -> Cout channels + ReLU reading NCHW images in place (image n at x + n
+ *    img_stride floats); w (Cout, 3, ksize, ksize) nn.Conv2d layout; H % 16 == 0, W % 16 == 0.
+ *  tocvp_dec_tapsum_k_f32: border-class tap sums of the collapsed decoder layer 0 for a ksize x ksize kernel:
+ *    out (ksize^2, Cout, Cin), class (cy, cx) per axis: c < ksize/2 = c pixels from the first row, ksize/2 = interior,
+ *    c > ksize/2 = ksize - 1 - c pixels from the last; w (Cout, Cin, ksize, ksize).
+ *  tocvp_dec_layer0_expand_f32: layer 0's output y (nimg, H, W, C) = relu?((cpos[y,x,c] + S[n, cls(y,x), c]) * scale[c]
+ *    + shift[c]), cpos (H, W, C) = conv0(pos) without bias, S (nimg, ksize^2, C) = tapsum * slot; H, W >= ksize, C % 4 == 0.
+ * ------------------------------------------------------------------------------------------- */
+int tocvp_convk_f32(const float* x, const float* wp, const float* scale, const float* shift, float* y, int nimg, int SH,
+                    int SW, int Cin, int Cout, int ksize, int relu, int upsample2, void* stream);
+int tocvp_convk_f16x3_f32(const float* x, const void* wfrag, const float* scale, const float* shift, float* y, int nimg,
+                          int SH, int SW, int Cin, int Cout, int ksize, int relu, int upsample2, void* stream);
+int tocvp_convk_in3_f32(const float* x, long long img_stride, const float* w, const float* bias, float* y, int nimg,
+                        int H, int W, int Cout, int ksize, void* stream);
+int tocvp_dec_tapsum_k_f32(const float* w, float* out, int Cout, int Cin, int ksize, void* stream);
+int tocvp_dec_layer0_expand_f32(const float* cpos, const float* S, const float* scale, const float* shift, float* y,
+                                int nimg, int H, int W, int C, int ksize, int relu, void* stream);
 int tocvp_slot_composite_f32(const float* decoded, float* recons, float* masks, int B, int K, int N,
                              int F, int ld, void* stream);
 int tocvp_bilinear_resize_f32(const float* x, float* y, int n, int C, int cstride, int SH, int SW,

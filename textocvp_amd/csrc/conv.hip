@@ -210,6 +210,120 @@ __global__ __launch_bounds__(256) void conv5x5_in3_kernel(const float* __restric
     }
 }
 
+// first encoder layer of the SAVi variants: 3 -> Cout (32 / 64 / 128) channels, kernel KS (3, 5, 7, pad KS / 2), same
+// 16 x 16 pixel tile and VALU arithmetic as conv5x5_in3_kernel; blockIdx.z = 32-output-channel block
+template <int KS>
+__global__ __launch_bounds__(256) void convk_in3_kernel(const float* __restrict__ x, long long img_stride,
+                                                        const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ y, int H, int W, int Cout) {
+    constexpr int CO = 32, IS = 16 + KS - 1, KK = KS * KS;
+    __shared__ float in_s[3][IS][IS];
+    __shared__ __attribute__((aligned(16))) float w_s[3 * KK * CO];
+    const int t = threadIdx.x;
+    const int tiles_x = W / 16;
+    const int img = blockIdx.y, co0 = blockIdx.z * CO;
+    const int ty0 = (blockIdx.x / tiles_x) * 16, tx0 = (blockIdx.x % tiles_x) * 16;
+    const float* xi = x + (size_t)img * img_stride;
+
+    for (int i = t; i < 3 * KK * CO; i += 256) {
+        const int co = i / (3 * KK), k = i % (3 * KK);     // w[co0 + co][ci][dy][dx], k = ci*KK + dy*KS + dx
+        w_s[k * CO + co] = w[(size_t)co0 * 3 * KK + i];
+    }
+    for (int i = t; i < 3 * IS * IS; i += 256) {
+        const int ci = i / (IS * IS), rem = i % (IS * IS);
+        const int iy = ty0 + rem / IS - KS / 2, ix = tx0 + rem % IS - KS / 2;
+        float v = 0.f;
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = xi[((size_t)ci * H + iy) * W + ix];
+        in_s[ci][rem / IS][rem % IS] = v;
+    }
+    __syncthreads();
+
+    const int py = t >> 4, px = t & 15;
+    f32x4 acc[CO / 4];
+#pragma unroll
+    for (int c = 0; c < CO / 4; ++c)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[c][u] = bias[co0 + 4 * c + u];
+    for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+        for (int dy = 0; dy < KS; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < KS; ++dx) {
+                const float v = in_s[ci][py + dy][px + dx];
+                const float* wk = w_s + (ci * KK + dy * KS + dx) * CO;
+#pragma unroll
+                for (int c = 0; c < CO / 4; ++c)
+                    acc[c] += v * *reinterpret_cast<const f32x4*>(wk + 4 * c);
+            }
+    float* yo = y + (((size_t)img * H + ty0 + py) * W + tx0 + px) * Cout + co0;
+#pragma unroll
+    for (int c = 0; c < CO / 4; ++c) {
+        f32x4 v = acc[c];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = fmaxf(v[u], 0.f);
+        *reinterpret_cast<f32x4*>(yo + 4 * c) = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// collapsed layer 0 of the SAVi decoder variants (kernel KS, KS x KS border classes, any width):
+//   tapsum: out[cls = cy KS + cx, co, ci] = sum of w[co, ci, dy, dx] over the taps valid for border class (cy, cx);
+//           class c < KS / 2: c pixels from the first row / column, c == KS / 2: interior, c > KS / 2: KS - 1 - c from
+//           the last (needs H, W >= KS).
+//   expand: y[n, y, x, c] = relu?((cpos[y, x, c] + S[n, cls(y, x), c]) * scale[c] + shift[c]) -- layer 0's OUTPUT at the
+//           broadcast resolution; SAVi.broadcast's (B K, D, H, W) input is never formed.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void classk_range(int cls, int ks, int& lo, int& hi) {
+    const int r = ks / 2;
+    lo = cls < r ? r - cls : 0;
+    hi = cls > r ? r + (ks - 1 - cls) : ks - 1;
+}
+
+__device__ __forceinline__ int border_class_k(int p, int n, int ks) {
+    const int r = ks / 2;
+    return p < r ? p : (p >= n - r ? ks - 1 - (n - 1 - p) : r);
+}
+
+__global__ __launch_bounds__(256) void dec_tapsum_k_kernel(const float* __restrict__ w, float* __restrict__ out,
+                                                           int Cout, int Cin, int ks) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)ks * ks * Cout * Cin) return;
+    const int ci = (int)(i % Cin);
+    const int co = (int)((i / Cin) % Cout);
+    const int cls = (int)(i / ((long)Cin * Cout));
+    int ylo, yhi, xlo, xhi;
+    classk_range(cls / ks, ks, ylo, yhi);
+    classk_range(cls % ks, ks, xlo, xhi);
+    const float* wk = w + ((size_t)co * Cin + ci) * ks * ks;
+    double s = 0.0;                                          // summed in fp64, rounded once
+    for (int ty = ylo; ty <= yhi; ++ty)
+        for (int tx = xlo; tx <= xhi; ++tx) s += (double)wk[ty * ks + tx];
+    out[i] = (float)s;
+}
+
+__global__ __launch_bounds__(256) void dec_layer0_expand_kernel(const float* __restrict__ cpos, const float* __restrict__ S,
+                                                                const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, float* __restrict__ y,
+                                                                long total4, int H, int W, int C, int ks, int relu) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int C4 = C / 4;
+    const int c = (int)(i % C4) * 4;
+    const long pix = i / C4;
+    const int xx = (int)(pix % W), yy = (int)((pix / W) % H);
+    const long n = pix / ((long)H * W);
+    const int cls = border_class_k(yy, H, ks) * ks + border_class_k(xx, W, ks);
+    const f32x4 p = *reinterpret_cast<const f32x4*>(cpos + ((size_t)yy * W + xx) * C + c);
+    const f32x4 sv = *reinterpret_cast<const f32x4*>(S + ((size_t)n * ks * ks + cls) * C + c);
+    f32x4 v;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        float a = fmaf(p[u] + sv[u], scale ? scale[c + u] : 1.f, shift[c + u]);
+        v[u] = relu ? fmaxf(a, 0.f) : a;
+    }
+    *reinterpret_cast<f32x4*>(y + (size_t)i * 4) = v;
+}
+
 // ------------------------------------------------------------------------------------------
 // decoder tail: conv3x3 (64 -> 4) per slot image, softmax over slots, compositing
 // one thread = one pixel of an 8 x 16 tile, loops over the K slot images of its frame
@@ -226,6 +340,8 @@ constexpr int DT_ABL = TOCVP_DT_ABLATE;
 constexpr int DT_H = 16, DT_W = 16, DT_C = 64, DT_CC = 32, DT_CS = DT_CC + 4;
 constexpr int DT_IH = DT_H + 2, DT_IW = DT_W + 2;
 
+// C: input channels (hidden_dims[0] of the decoder: 64 as shipped, 32 / 128 for the SAVi variants), in C / 32 passes
+template <int C = DT_C>
 __global__ __launch_bounds__(256, 3) void dec_tail_kernel(const float* __restrict__ x,
                                                           const float* __restrict__ wq,
                                                           const float* __restrict__ bias,
@@ -258,8 +374,9 @@ __global__ __launch_bounds__(256, 3) void dec_tail_kernel(const float* __restric
     // FMAs of step s (its ~2 us of memory latency then runs under ~1 us of FMAs here plus the partner
     // workgroup's), instead of in front of its own barrier.
     f32x4 tv[NIT];
+    constexpr int NP = C / DT_CC;                                   // passes per slot image
     auto fetch = [&](int step) {
-        const float* xi = x + ((size_t)f * K + (step >> 1)) * HW * DT_C + (step & 1) * DT_CC;
+        const float* xi = x + ((size_t)f * K + step / NP) * HW * C + (step % NP) * DT_CC;
         if (DT_ABL == 1 && step > 0) return;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {                          // batched, clamped loads
@@ -267,14 +384,14 @@ __global__ __launch_bounds__(256, 3) void dec_tail_kernel(const float* __restric
             const int p = i / F4, c = (i % F4) * 4;
             const int iy = min(max(ty0 + p / DT_IW - 1, 0), H - 1);
             const int ix = min(max(tx0 + p % DT_IW - 1, 0), W - 1);
-            tv[it] = *reinterpret_cast<const f32x4*>(xi + ((size_t)iy * W + ix) * DT_C + c);
+            tv[it] = *reinterpret_cast<const f32x4*>(xi + ((size_t)iy * W + ix) * C + c);
         }
     };
     fetch(0);
     f32x4 acc = bv;
 #pragma unroll 1
-    for (int step = 0; step < 2 * K; ++step) {
-        const int k = step >> 1, pass = step & 1;
+    for (int step = 0; step < NP * K; ++step) {
+        const int k = step / NP, pass = step % NP;
         __syncthreads();                                            // previous step consumed
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
@@ -290,11 +407,11 @@ __global__ __launch_bounds__(256, 3) void dec_tail_kernel(const float* __restric
             }
         }
         __syncthreads();
-        if (step + 1 < 2 * K) fetch(step + 1);
+        if (step + 1 < NP * K) fetch(step + 1);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const float* ip = in_s + ((py + tap / 3) * DT_IW + px + tap % 3) * DT_CS;
-            const float* wt = wq + ((size_t)tap * DT_C + pass * DT_CC) * 4;       // wave-uniform
+            const float* wt = wq + ((size_t)tap * C + pass * DT_CC) * 4;          // wave-uniform
 #pragma unroll
             for (int c4 = 0; c4 < DT_CC / 4; ++c4) {
                 const f32x4 xv = *reinterpret_cast<const f32x4*>(ip + 4 * c4);
@@ -312,7 +429,7 @@ __global__ __launch_bounds__(256, 3) void dec_tail_kernel(const float* __restric
                 }
             }
         }
-        if (pass == 1) {
+        if (pass == NP - 1) {
             float* ro = recons + (size_t)f * rec_fs + (size_t)k * 3 * HW + pix;
             ro[0] = acc[0];
             ro[HW] = acc[1];
@@ -411,20 +528,28 @@ extern "C" int tocvp_dec_tail_placed_f32(const float* x, const float* w, const f
                                          long mask_fs, int F, int K, int H, int W, int Cin, void* ws, size_t ws_bytes,
                                          void* stream) {
     TOCVP_CHECK_ARG(x && w && bias && recons_imgs && recons && masks && ws);
-    TOCVP_CHECK_ARG(F >= 0 && F <= 65535 && K > 0 && K <= 32 && Cin == DT_C);
+    TOCVP_CHECK_ARG(F >= 0 && F <= 65535 && K > 0 && K <= 32);
+    if (Cin != 32 && Cin != 64 && Cin != 128) return TOCVP_EINVAL;
     TOCVP_CHECK_ARG((H % DT_H) == 0 && (W % DT_W) == 0);
-    TOCVP_CHECK_ARG(ws_bytes >= (size_t)9 * DT_C * 4 * sizeof(float));
+    TOCVP_CHECK_ARG(ws_bytes >= (size_t)9 * Cin * 4 * sizeof(float));
     TOCVP_CHECK_ARG(img_fs >= 3L * H * W && rec_fs >= 3L * K * H * W && mask_fs >= (long)K * H * W);
     if (!tocvp_aligned16(x) || !tocvp_aligned16(ws)) return TOCVP_EALIGN;
     if (F == 0) return TOCVP_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* wq = static_cast<float*>(ws);
-    hipLaunchKernelGGL(dec_tail_pack_kernel, dim3((9 * DT_C * 4 + 255) / 256), dim3(256), 0, s, w, wq,
-                       DT_C);
+    hipLaunchKernelGGL(dec_tail_pack_kernel, dim3((9 * Cin * 4 + 255) / 256), dim3(256), 0, s, w, wq,
+                       Cin);
     if (hipGetLastError() != hipSuccess) return TOCVP_ELAUNCH;
-    hipLaunchKernelGGL(dec_tail_kernel, dim3((H / DT_H) * (W / DT_W) * ((F + 7) / 8 * 8)), dim3(256), 0, s, x,
-                       static_cast<const float*>(wq), bias, recons_imgs, recons, masks, clamped_imgs, img_fs, rec_fs,
-                       mask_fs, F, K, H, W);
+    const dim3 grid((H / DT_H) * (W / DT_W) * ((F + 7) / 8 * 8));
+    if (Cin == 64)
+        hipLaunchKernelGGL(dec_tail_kernel<64>, grid, dim3(256), 0, s, x, static_cast<const float*>(wq), bias, recons_imgs,
+                           recons, masks, clamped_imgs, img_fs, rec_fs, mask_fs, F, K, H, W);
+    else if (Cin == 32)
+        hipLaunchKernelGGL(dec_tail_kernel<32>, grid, dim3(256), 0, s, x, static_cast<const float*>(wq), bias, recons_imgs,
+                           recons, masks, clamped_imgs, img_fs, rec_fs, mask_fs, F, K, H, W);
+    else
+        hipLaunchKernelGGL(dec_tail_kernel<128>, grid, dim3(256), 0, s, x, static_cast<const float*>(wq), bias,
+                           recons_imgs, recons, masks, clamped_imgs, img_fs, rec_fs, mask_fs, F, K, H, W);
     return tocvp_launch_status();
 }
 
@@ -433,4 +558,40 @@ extern "C" int tocvp_dec_tail_f32(const float* x, const float* w, const float* b
                                   int H, int W, int Cin, void* ws, size_t ws_bytes, void* stream) {
     return tocvp_dec_tail_placed_f32(x, w, bias, recons_imgs, recons, masks, nullptr, 3L * H * W, 3L * K * H * W,
                                      (long)K * H * W, F, K, H, W, Cin, ws, ws_bytes, stream);
+}
+
+extern "C" int tocvp_convk_in3_f32(const float* x, long long img_stride, const float* w, const float* bias, float* y,
+                                   int nimg, int H, int W, int Cout, int ksize, void* stream) {
+    TOCVP_CHECK_ARG(x && w && bias && y);
+    TOCVP_CHECK_ARG(ksize == 3 || ksize == 5 || ksize == 7);
+    TOCVP_CHECK_ARG(nimg >= 0 && nimg <= 65535 && (H % 16) == 0 && (W % 16) == 0);
+    if (Cout != 32 && Cout != 64 && Cout != 128) return TOCVP_EINVAL;
+    if (!tocvp_aligned16(y)) return TOCVP_EALIGN;
+    if (nimg == 0) return TOCVP_OK;
+    const dim3 grid((H / 16) * (W / 16), nimg, Cout / 32);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ksize == 3) hipLaunchKernelGGL(convk_in3_kernel<3>, grid, dim3(256), 0, s, x, img_stride, w, bias, y, H, W, Cout);
+    else if (ksize == 5) hipLaunchKernelGGL(convk_in3_kernel<5>, grid, dim3(256), 0, s, x, img_stride, w, bias, y, H, W, Cout);
+    else hipLaunchKernelGGL(convk_in3_kernel<7>, grid, dim3(256), 0, s, x, img_stride, w, bias, y, H, W, Cout);
+    return tocvp_launch_status();
+}
+
+extern "C" int tocvp_dec_tapsum_k_f32(const float* w, float* out, int Cout, int Cin, int ksize, void* stream) {
+    TOCVP_CHECK_ARG(w && out && Cout > 0 && Cin > 0 && (ksize == 3 || ksize == 5 || ksize == 7));
+    const long total = (long)ksize * ksize * Cout * Cin;
+    hipLaunchKernelGGL(dec_tapsum_k_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), w, out, Cout, Cin, ksize);
+    return tocvp_launch_status();
+}
+
+extern "C" int tocvp_dec_layer0_expand_f32(const float* cpos, const float* S, const float* scale, const float* shift,
+                                           float* y, int nimg, int H, int W, int C, int ksize, int relu, void* stream) {
+    TOCVP_CHECK_ARG(cpos && S && shift && y && (ksize == 3 || ksize == 5 || ksize == 7));
+    TOCVP_CHECK_ARG(nimg >= 0 && H >= ksize && W >= ksize && C > 0 && (C % 4) == 0);
+    if (!tocvp_aligned16(cpos) || !tocvp_aligned16(S) || !tocvp_aligned16(y)) return TOCVP_EALIGN;
+    const long total4 = (long)nimg * H * W * (C / 4);
+    if (total4 == 0) return TOCVP_OK;
+    hipLaunchKernelGGL(dec_layer0_expand_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), cpos, S, scale, shift, y, total4, H, W, C, ksize, relu);
+    return tocvp_launch_status();
 }

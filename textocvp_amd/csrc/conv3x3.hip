@@ -12,24 +12,34 @@
 //                          (decoders.py:279-283).
 //  bilinear_resize_kernel: F.interpolate(mode='bilinear', align_corners=False) of the image head
 //                          (decoders.py:291-297), NHWC in -> NCHW out.
+//
+// The same two convolutions also run the SAVi encoder / decoder variants (tocvp_convk_f32, tocvp_convk_f16x3_f32): kernel
+// 3 / 5 / 7, nearest x2 upsampling of the input (fp32: through the tile loader; f16x3: four phase convolutions over the
+// source image), widths 32 / 64 / 128.
 #include "common.h"
 
 namespace {
 
-constexpr int TH = 8, TW = 32, IH = TH + 2, IW = TW + 2;    // IH / IW: 3x3 fp32 kernel (split kernel: per KS)
-constexpr int CC = 64, CS = CC + 4;
+constexpr int TH = 8, TW = 32;       // output tile (halo sizes per kernel size inside the kernels)
+constexpr int CC = 64;
 
 struct Conv3Args {
     const float* x; const float* wp; const float* scale; const float* shift; float* y;
     int nimg, H, W, Cin, Cout, relu, upsample;   // H, W = OUTPUT (= conv input after upsampling) size
 };
 
-template <int NB>   // 32-channel output blocks per workgroup (2 -> 64 channels, 1 -> 32)
+// NB: 32-channel output blocks per workgroup (2 -> 64 channels, 1 -> 32).  KS, CCK: kernel size (pad KS / 2) and input
+// channels per LDS chunk -- 3 / 64 for the image head; the SAVi variants (tocvp_convk_f32) take KS 3, 5, 7 in 32-channel
+// chunks (KS 7: 14 x 38 x 36 floats of halo + 2 x 64 x 36 of weights = 95 KB).  upsample: the nearest x2 upsampling
+// of the input is read through the tile loader (the conv runs over the upsampled grid).
+template <int NB, int KS = 3, int CCK = CC>
 __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
+    constexpr int IH = TH + KS - 1, IW = TW + KS - 1, CS = CCK + 4, NTAP = KS * KS;
     constexpr int COUTB = NB * 32;
-    constexpr int F4 = CC / 4;
+    constexpr int F4 = CCK / 4;
     constexpr int WREG = (COUTB * F4) / 256;
     constexpr int NIT = (IH * IW * F4 + 255) / 256;
+    static_assert((COUTB * F4) % 256 == 0, "weight slice must split evenly over the workgroup");
     __shared__ __attribute__((aligned(16))) float lds[IH * IW * CS + 2 * COUTB * CS];
     float* in_s = lds;
     float* w_s = lds + IH * IW * CS;
@@ -58,7 +68,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
             const int idx = t + 256 * i;
             const int co = idx / F4, c = (idx % F4) * 4;
             wreg[i] = *reinterpret_cast<const f32x4*>(p.wp + ((size_t)tap * p.Cout + co0 + co) * p.Cin +
-                                                      ch * CC + c);
+                                                      ch * CCK + c);
         }
     };
     auto wstore = [&](int buf) {
@@ -70,7 +80,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
         }
     };
 
-    const int nch = p.Cin / CC;
+    const int nch = p.Cin / CCK;
     for (int ch = 0; ch < nch; ++ch) {
         // halo tile of this channel chunk: batched loads from clamped addresses, zeroed outside
         f32x4 tv[NIT];
@@ -78,10 +88,10 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
         for (int it = 0; it < NIT; ++it) {
             const int i = min(t + it * 256, IH * IW * F4 - 1);
             const int pix = i / F4, c = (i % F4) * 4;
-            const int iy = min(max(ty0 + pix / IW - 1, 0), p.H - 1) >> sh;
-            const int ix = min(max(tx0 + pix % IW - 1, 0), p.W - 1) >> sh;
+            const int iy = min(max(ty0 + pix / IW - KS / 2, 0), p.H - 1) >> sh;
+            const int ix = min(max(tx0 + pix % IW - KS / 2, 0), p.W - 1) >> sh;
             tv[it] = *reinterpret_cast<const f32x4*>(p.x + (((size_t)img * SH + iy) * SW + ix) * p.Cin +
-                                                     ch * CC + c);
+                                                     ch * CCK + c);
         }
         wload(0, ch);
         __syncthreads();   // previous chunk fully consumed
@@ -90,7 +100,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
             const int i = t + it * 256;
             if (i < IH * IW * F4) {
                 const int pix = i / F4, c = (i % F4) * 4;
-                const int iy = ty0 + pix / IW - 1, ix = tx0 + pix % IW - 1;
+                const int iy = ty0 + pix / IW - KS / 2, ix = tx0 + pix % IW - KS / 2;
                 const bool inside = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
                 f32x4 v = tv[it];
 #pragma unroll
@@ -101,15 +111,15 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
         wstore(0);
         __syncthreads();
 
-        for (int tap = 0; tap < 9; ++tap) {
+        for (int tap = 0; tap < NTAP; ++tap) {
             const int buf = tap & 1;
-            if (tap + 1 < 9) wload(tap + 1, ch);
+            if (tap + 1 < NTAP) wload(tap + 1, ch);
             __builtin_amdgcn_sched_barrier(0);
-            const int dy = tap / 3, dx = tap % 3;
+            const int dy = tap / KS, dx = tap % KS;
             const float* a_base = in_s + ((2 * wave + dy) * IW + l31 + dx) * CS + 4 * h;
             const float* b_base = w_s + buf * COUTB * CS + l31 * CS + 4 * h;
 #pragma unroll
-            for (int j = 0; j < CC / 8; ++j) {
+            for (int j = 0; j < CCK / 8; ++j) {
                 f32x4 a[2], b[NB];
                 a[0] = *reinterpret_cast<const f32x4*>(a_base + 8 * j);
                 a[1] = *reinterpret_cast<const f32x4*>(a_base + IW * CS + 8 * j);
@@ -123,7 +133,7 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(Conv3Args p) {
 #pragma unroll
                         for (int n = 0; n < NB; ++n) acc[m][n] = mfma32(a[m][u], b[n][u], acc[m][n]);
             }
-            if (tap + 1 < 9) wstore(buf ^ 1);
+            if (tap + 1 < NTAP) wstore(buf ^ 1);
             __syncthreads();
         }
     }
@@ -184,13 +194,20 @@ __device__ __forceinline__ void split4_f16(f32x4 v, float scale, unsigned char* 
 // tap sums.  p.H, p.W = source size, weights (4 phases, 4 taps, Cout, Cin), output (nimg, 2 H, 2 W, Cout).
 // NARROW: images at most 16 pixels wide (the 16 x 16 patch grid of the image head): a 16 x 16 pixel tile whose 32-pixel MFMA
 // blocks hold TWO image rows of 16 pixels instead of one row of 32 (an 8 x 32 tile would compute 16 columns of padding).
-template <int NB, int KS, bool NARROW = false>
+//
+// KU > 0: the phase form of "nearest x2 upsampling -> KU x KU conv (pad KU / 2)" for any odd KU (SAVi decoders with
+// upsample 2).  Output row 2 y + a reads source rows y + floor((a + d) / 2), d in [-KU / 2, KU / 2]: KS = KU / 2 + 1 taps per
+// phase and direction starting at floor((a - KU / 2) / 2) (KU 3: 2x2 phases from -1 / 0, KU 5: 3x3 from -1 / -1, KU 7: 4x4
+// from -2 / -1).  Weights (4 phases, KS * KS taps, Cout, Cin) from kernels.pack_conv_up2_weights.  KS == 2 alone is KU = 3.
+template <int NB, int KS, bool NARROW = false, int KU = (KS == 2 ? 3 : 0)>
 __global__ __launch_bounds__(256, 2) void convk_f16x3_kernel(Conv3Args p) {
-    constexpr bool PH = KS == 2;
+    constexpr bool PH = KU > 0;
+    static_assert(!PH || KS == KU / 2 + 1, "phase form: KU / 2 + 1 taps per direction");
     constexpr int TH_ = NARROW ? 16 : TH, TW_ = NARROW ? 16 : TW;
     constexpr int IH = TH_ + KS - 1, IW = TW_ + KS - 1, NTAP = KS * KS;
     const int pa = PH ? (int)blockIdx.z >> 1 : 0, pb = PH ? (int)blockIdx.z & 1 : 0;
-    const int oy0 = PH ? pa - 1 : -(KS / 2), ox0 = PH ? pb - 1 : -(KS / 2);     // first tap relative to the output pixel
+    // first tap relative to the output pixel; floor((a - KU / 2) / 2) written for non-negative division
+    const int oy0 = PH ? (pa - KU / 2 + 2 * KU) / 2 - KU : -(KS / 2), ox0 = PH ? (pb - KU / 2 + 2 * KU) / 2 - KU : -(KS / 2);
     constexpr int COUTB = NB * 32;
     constexpr int F4 = CH / 4;
     constexpr int NIT = (IH * IW * F4 + 255) / 256;
@@ -255,10 +272,12 @@ __global__ __launch_bounds__(256, 2) void convk_f16x3_kernel(Conv3Args p) {
         }
         __syncthreads();
 
-        // the taps of a chunk, fully unrolled (LDS offsets are immediates, no barrier inside): (ch, tap, ks) order as before
+        // the taps of a chunk, fully unrolled (LDS offsets are immediates, no barrier inside): (ch, tap, ks) order as before.
+        // KS 7: one kernel row per unrolled body (49 unrolled taps spill at NB = 2)
+        constexpr int TAP_UNROLL = KS >= 7 ? KS : NTAP;
         const unsigned char* wch = wf_base + ((size_t)(PH ? (int)blockIdx.z * NTAP : 0) * rb_tap + rb0) * KC * 2048 +
                                    (size_t)ch * (CH / 16) * 2048;
-#pragma unroll
+#pragma unroll TAP_UNROLL
         for (int tap = 0; tap < NTAP; ++tap) {
             const int dy = tap / KS, dx = tap % KS;
             const unsigned char* a_base = in_s + ((WROWS * wave + apy + dy) * IW + apx + dx) * ROWB + h * 16;
@@ -451,6 +470,81 @@ extern "C" int tocvp_conv5x5_f16x3_f32(const float* x, const void* wp, const flo
                                        int nimg, int H, int W, int Cin, int Cout, int relu,
                                        void* stream) {
     return launch_convk_f16x3(x, static_cast<const float*>(wp), nullptr, bias, y, nimg, H, W, Cin, Cout, relu, 0, 5, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// SAVi encoder / decoder variants (kernel 3, 5, 7, optional nearest x2 upsampling of the input, 32 / 64 / 128 channels)
+// ------------------------------------------------------------------------------------------------
+static bool savi_width(int c) { return c == 32 || c == 64 || c == 128; }
+
+template <int KS, int CCK>
+static void launch_convk_f32_ks(const Conv3Args& a, size_t tiles, hipStream_t s) {
+    if (a.Cout % 64 == 0)
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<2, KS, CCK>), dim3((unsigned)(a.nimg * tiles), a.Cout / 64), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((conv3x3_mfma_kernel<1, KS, CCK>), dim3((unsigned)(a.nimg * tiles), a.Cout / 32), dim3(256), 0, s, a);
+}
+
+extern "C" int tocvp_convk_f32(const float* x, const float* wp, const float* scale, const float* shift, float* y,
+                               int nimg, int SH, int SW, int Cin, int Cout, int ksize, int relu, int upsample2,
+                               void* stream) {
+    TOCVP_CHECK_ARG(x && wp && shift && y);
+    TOCVP_CHECK_ARG(ksize == 3 || ksize == 5 || ksize == 7);
+    TOCVP_CHECK_ARG(nimg >= 0 && SH > 0 && SW > 0);
+    if (!savi_width(Cin) || !savi_width(Cout)) return TOCVP_EINVAL;
+    const int H = upsample2 ? 2 * SH : SH, W = upsample2 ? 2 * SW : SW;           // conv (= output) grid
+    TOCVP_CHECK_ARG((H % TH) == 0);
+    const size_t tiles = (size_t)((W + TW - 1) / TW) * (H / TH);
+    TOCVP_CHECK_ARG(nimg * tiles < 0x7fffffffu);
+    if (!tocvp_aligned16(x) || !tocvp_aligned16(wp)) return TOCVP_EALIGN;
+    if (nimg == 0) return TOCVP_OK;
+    Conv3Args a{x, wp, scale, shift, y, nimg, H, W, Cin, Cout, relu, upsample2 ? 1 : 0};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ksize == 3) launch_convk_f32_ks<3, 32>(a, tiles, s);
+    else if (ksize == 5) launch_convk_f32_ks<5, 32>(a, tiles, s);
+    else launch_convk_f32_ks<7, 32>(a, tiles, s);
+    return tocvp_launch_status();
+}
+
+template <int KS, int KU>
+static void launch_convk_f16x3_ks(const Conv3Args& a, hipStream_t s) {
+    constexpr unsigned PHASES = KU > 0 ? 4 : 1;
+    const unsigned ncb64 = a.Cout / 64, ncb32 = a.Cout / 32;
+    if (a.W <= 16 && (a.H % 16) == 0) {                            // narrow images: 16 x 16 tiles (two rows per MFMA block)
+        const unsigned nt = (unsigned)(a.nimg * (size_t)(a.H / 16));
+        if (a.Cout % 64 == 0) hipLaunchKernelGGL((convk_f16x3_kernel<2, KS, true, KU>), dim3(nt, ncb64, PHASES), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((convk_f16x3_kernel<1, KS, true, KU>), dim3(nt, ncb32, PHASES), dim3(256), 0, s, a);
+        return;
+    }
+    const unsigned nt = (unsigned)(a.nimg * (size_t)((a.W + TW - 1) / TW) * (a.H / TH));
+    if (a.Cout % 64 == 0) hipLaunchKernelGGL((convk_f16x3_kernel<2, KS, false, KU>), dim3(nt, ncb64, PHASES), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((convk_f16x3_kernel<1, KS, false, KU>), dim3(nt, ncb32, PHASES), dim3(256), 0, s, a);
+}
+
+extern "C" int tocvp_convk_f16x3_f32(const float* x, const void* wfrag, const float* scale, const float* shift, float* y,
+                                     int nimg, int SH, int SW, int Cin, int Cout, int ksize, int relu, int upsample2,
+                                     void* stream) {
+    TOCVP_CHECK_ARG(x && wfrag && shift && y);
+    TOCVP_CHECK_ARG(ksize == 3 || ksize == 5 || ksize == 7);
+    TOCVP_CHECK_ARG(nimg >= 0 && SH > 0 && SW > 0 && (SH % TH) == 0);
+    if (!savi_width(Cin) || !savi_width(Cout)) return TOCVP_EINVAL;
+    const size_t tiles = (size_t)((SW + TW - 1) / TW) * (SH / TH);
+    TOCVP_CHECK_ARG(nimg * tiles < 0x7fffffffu);
+    if (!tocvp_aligned16(x) || !tocvp_aligned16(wfrag)) return TOCVP_EALIGN;
+    if (nimg == 0) return TOCVP_OK;
+    // the kernel sees the SOURCE grid (the phase form writes the 2 SH x 2 SW output itself)
+    Conv3Args a{x, static_cast<const float*>(wfrag), scale, shift, y, nimg, SH, SW, Cin, Cout, relu, 0};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!upsample2) {
+        if (ksize == 3) launch_convk_f16x3_ks<3, 0>(a, s);
+        else if (ksize == 5) launch_convk_f16x3_ks<5, 0>(a, s);
+        else launch_convk_f16x3_ks<7, 0>(a, s);
+    } else {
+        if (ksize == 3) launch_convk_f16x3_ks<2, 3>(a, s);
+        else if (ksize == 5) launch_convk_f16x3_ks<3, 5>(a, s);
+        else launch_convk_f16x3_ks<4, 7>(a, s);
+    }
+    return tocvp_launch_status();
 }
 
 extern "C" int tocvp_slot_composite_f32(const float* decoded, float* recons, float* masks, int B,

@@ -77,6 +77,20 @@ _SIGNATURES = {
     "tocvp_gemm_f16chunk_f32": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_convk_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_convk_f16x3_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_convk_in3_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_dec_tapsum_k_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_dec_layer0_expand_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "tocvp_conv3x3_up2_f16x3_f32": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -1698,6 +1712,116 @@ def conv3x3_up2(x, wphase, scale, shift, relu=True):
     _timed(lambda: f"conv3x3_up2_{n}x{SH}x{SW}x{Cin}x{Cout}", 2.0 * n * SH * SW * 16 * Cin * Cout, lambda: _check(
         lib().tocvp_conv3x3_up2_f16x3_f32(_ptr(x), _ptr(conv_frag_weights(wphase)), _ptr(scale), _ptr(shift), _ptr(y), n, SH, SW, Cin, Cout,
                                           int(bool(relu)), _stream()), "tocvp_conv3x3_up2_f16x3_f32"))
+    return y
+
+
+# ---- SAVi encoder / decoder variants (kernel 3 / 5 / 7, nearest x2 upsampling, widths 32 / 64 / 128) -------------------
+SAVI_WIDTHS = (32, 64, 128)
+
+
+def _up2_rows(k, a):
+    """ taps d (index d + k // 2) of a k-tap conv over the x2-upsampled axis that read source offset floor((a + d) / 2),
+    grouped per phase tap i (offset floor((a - k // 2) / 2) + i) """
+    r = k // 2
+    first = (a - r) // 2
+    rows = [[] for _ in range(r + 1)]
+    for d in range(-r, r + 1):
+        rows[(a + d) // 2 - first].append(d + r)
+    return rows
+
+
+def pack_conv_up2_weights(weight):
+    """
+    (Cout, Cin, k, k), k odd -> (4 phases, T * T taps, Cout, Cin), T = k // 2 + 1, for convk(..., upsample2=True) in f16x3:
+    phase (a, b) = output pixel (2 y + a, 2 x + b) of "nearest x2 -> k x k conv (pad k // 2)"; its tap (i, j) reads source
+    pixel (y + floor((a - k // 2) / 2) + i, x + floor((b - k // 2) / 2) + j) and holds the sum of the k x k taps that fall
+    on that pixel (summed in float64, rounded once).  k = 3 gives the layout of pack_conv3x3_up2_weights.
+    """
+    k = int(weight.shape[-1])
+    assert k % 2 == 1 and weight.shape[-2] == k
+    T = k // 2 + 1
+    w = weight.detach().double()
+    out = torch.empty((4, T * T) + tuple(w.shape[:2]), device=w.device, dtype=torch.float64)
+    for a in range(2):
+        ra = _up2_rows(k, a)
+        for b in range(2):
+            rb = _up2_rows(k, b)
+            for i in range(T):
+                for j in range(T):
+                    out[2 * a + b, T * i + j] = sum(w[:, :, dy, dx] for dy in ra[i] for dx in rb[j])
+    return out.float().contiguous()
+
+
+def convk(x, wk, scale, shift, ksize, relu=True, upsample2=False, precision="f16x3"):
+    """
+    SAVi variant convolution: NHWC (n, SH, SW, Cin) -> (n, H, W, Cout), H, W = SH, SW or 2 SH, 2 SW with upsample2 (nearest
+    x2 upsampling of the input, never materialised), kernel ksize in {3, 5, 7} with pad ksize // 2, per-channel scale (may be
+    None) / shift epilogue (+ ReLU).  Cin, Cout in {32, 64, 128}.
+      precision "f16x3": split fp16 operands (fp32-class, |x| < 255, |w| < 63); wk = pack_conv_weights(w), or
+                         pack_conv_up2_weights(w) with upsample2 (four phase convolutions over the source image);
+      precision "fp32":  fp32 MFMA; wk = pack_conv_weights(w) (the upsampling is read through the tile loader).
+    """
+    n, SH, SW, Cin = x.shape
+    Cout = wk.shape[-2]
+    H, W = (2 * SH, 2 * SW) if upsample2 else (SH, SW)
+    if Cin not in SAVI_WIDTHS or Cout not in SAVI_WIDTHS or ksize not in (3, 5, 7):
+        raise NotImplementedError(f"convk: widths {Cin} -> {Cout}, kernel {ksize} (widths {SAVI_WIDTHS}, kernels 3 / 5 / 7)")
+    assert x.is_contiguous() and wk.is_contiguous() and wk.shape[-1] == Cin
+    y = torch.empty((n, H, W, Cout), device=x.device, dtype=torch.float32)
+    if precision == "f16x3":
+        taps_shape = (4, (ksize // 2 + 1) ** 2) if upsample2 else (ksize * ksize,)
+        assert tuple(wk.shape) == taps_shape + (Cout, Cin), (tuple(wk.shape), taps_shape)
+        if _CHECK_RANGE:
+            _check_f16_range(absmax(x), f"convk{ksize} (f16x3) input")
+            _check_f16_weight_range(wk, f"convk{ksize} (f16x3)")
+        taps = 4 * (ksize // 2 + 1) ** 2 if upsample2 else ksize * ksize
+        flops = 2.0 * n * SH * SW * taps * Cin * Cout
+        _timed(lambda: f"convk{ksize}{'_up2' if upsample2 else ''}_f16x3_{n}x{SH}x{SW}x{Cin}x{Cout}", flops, lambda: _check(
+            lib().tocvp_convk_f16x3_f32(_ptr(x), _ptr(conv_frag_weights(wk)), _ptr(scale), _ptr(shift), _ptr(y), n, SH, SW,
+                                        Cin, Cout, ksize, int(bool(relu)), int(bool(upsample2)), _stream()),
+            "tocvp_convk_f16x3_f32"))
+    elif precision == "fp32":
+        assert wk.shape[0] == ksize * ksize and wk.dim() == 3
+        flops = 2.0 * n * H * W * ksize * ksize * Cin * Cout
+        _timed(lambda: f"convk{ksize}{'_up2' if upsample2 else ''}_fp32_{n}x{SH}x{SW}x{Cin}x{Cout}", flops, lambda: _check(
+            lib().tocvp_convk_f32(_ptr(x), _ptr(wk), _ptr(scale), _ptr(shift), _ptr(y), n, SH, SW, Cin, Cout, ksize,
+                                  int(bool(relu)), int(bool(upsample2)), _stream()), "tocvp_convk_f32"))
+    else:
+        raise NotImplementedError(f"convk: precision {precision!r} (f16x3 / fp32)")
+    return y
+
+
+def convk_in3(x, w, bias):
+    """ first encoder layer of the variants: x (n, 3, H, W) view of contiguous image planes, w (Cout, 3, k, k), k in
+    {3, 5, 7}, Cout in {32, 64, 128} -> NHWC (n, H, W, Cout) after ReLU """
+    n, C, H, W = x.shape
+    assert C == 3 and x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W
+    Cout, ksize = w.shape[0], w.shape[-1]
+    if Cout not in SAVI_WIDTHS or ksize not in (3, 5, 7):
+        raise NotImplementedError(f"convk_in3: width {Cout}, kernel {ksize}")
+    y = torch.empty((n, H, W, Cout), device=x.device, dtype=torch.float32)
+    _check(lib().tocvp_convk_in3_f32(_ptr(x), x.stride(0) if n > 1 else 3 * H * W, _ptr(w.contiguous()), _ptr(bias),
+                                     _ptr(y), n, H, W, Cout, ksize, _stream()), "tocvp_convk_in3_f32")
+    return y
+
+
+def dec_tapsum_k(w):
+    """ (Cout, Cin, k, k) -> (k * k, Cout, Cin) border-class tap sums of the collapsed decoder layer 0 (fp64 sums) """
+    Cout, Cin, k = w.shape[0], w.shape[1], w.shape[-1]
+    out = torch.empty((k * k, Cout, Cin), device=w.device, dtype=torch.float32)
+    _check(lib().tocvp_dec_tapsum_k_f32(_ptr(w.contiguous()), _ptr(out), Cout, Cin, k, _stream()), "tocvp_dec_tapsum_k_f32")
+    return out
+
+
+def dec_layer0_expand(cpos, S, scale, shift, ksize, relu=True):
+    """ cpos (H, W, C) = conv0(pos) without bias, S (n, k * k, C) = per-slot tap sums -> layer 0's output
+    (n, H, W, C) = relu((cpos + S[cls(y, x)]) * scale + shift) """
+    H, W, C = cpos.shape
+    n = S.shape[0]
+    assert cpos.is_contiguous() and S.is_contiguous() and tuple(S.shape[1:]) == (ksize * ksize, C)
+    y = torch.empty((n, H, W, C), device=cpos.device, dtype=torch.float32)
+    _check(lib().tocvp_dec_layer0_expand_f32(_ptr(cpos), _ptr(S), _ptr(scale), _ptr(shift), _ptr(y), n, H, W, C, ksize,
+                                             int(bool(relu)), _stream()), "tocvp_dec_layer0_expand_f32")
     return y
 
 

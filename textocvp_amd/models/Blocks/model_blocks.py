@@ -15,7 +15,8 @@ __all__ = ["ConvBlock", "Upsample", "SoftPositionEmbed", "TemporalPositionalEnco
 class Upsample(nn.Module):
     """
     Nearest-neighbour upsampling marker (model_blocks.py:23-45).  It owns no parameters; on the
-    MI355X path it is fused into the tile loader of the following convolution.
+    MI355X path it is fused into the following convolution (tile loader, or four phase convolutions
+    over the source image).  ConvDecoder places it between its blocks like the reference.
     """
 
     def __init__(self, scale_factor):

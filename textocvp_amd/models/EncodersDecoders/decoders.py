@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ... import kernels as K
 from ...precision import knob
-from ..Blocks.model_blocks import ConvBlock
+from ..Blocks.model_blocks import ConvBlock, Upsample
 from ..Blocks.model_utils import Derived
 
 # MLPPatchDecoder: hidden activations between its Linear layers as producer-written fp16 operand planes
@@ -50,23 +50,45 @@ class ConvDecoder(nn.Module):
       layer 2-3 tocvp_conv5x5_f32
       tail      tocvp_dec_tail_f32: conv3x3 + softmax over slots + compositing, writing the
                 reference's three output tensors directly.
+
+    Variants of the reference factory (kernel 3 / 7, ``upsample: 2``, ``batch_norm``, widths 32 / 64 / 128) take the
+    generic path (``_decode_generic``): layer 0 collapsed over k x k border classes, the hidden layers on
+    kernels.convk (nearest x2 upsampling as four phase convolutions over the source image, eval BatchNorm folded into
+    the epilogue), the exact fp32 tail at the output resolution ``resolution * 2 ** (L - 1)``.
     """
 
     def __init__(self, in_channels, hidden_dims, kernel_size=5, upsample=None, out_channels=4,
                  **kwargs):
         super().__init__()
-        if kernel_size != 5 or (upsample is not None and upsample >= 2) or kwargs.get("batch_norm"):
-            raise NotImplementedError("ConvDecoder: kernel 5, upsample < 2, no batch-norm")
+        upsample = None if upsample is None or upsample < 2 else upsample
+        batch_norm = bool(kwargs.get("batch_norm"))
+        if upsample is not None and upsample != 2:
+            raise NotImplementedError(f"ConvDecoder: upsample {upsample} (only nearest x2 is fused into the convs)")
+        if kwargs.get("stride", 1) != 1:
+            raise NotImplementedError("ConvDecoder: stride != 1")
+        if kernel_size not in (3, 5, 7):
+            raise NotImplementedError(f"ConvDecoder: kernel {kernel_size} (3, 5 or 7)")
         if out_channels != 4 or len(hidden_dims) < 2:
             raise NotImplementedError("ConvDecoder: RGB + alpha output, >= 2 hidden layers")
+        # the shipped configuration (k 5, no upsampling, no batch-norm) keeps its dedicated path; every other one runs
+        # the generic path, whose convs take 32 / 64 / 128 channels
+        self.generic = kernel_size != 5 or upsample is not None or batch_norm
+        if self.generic and any(c not in K.SAVI_WIDTHS for c in list(hidden_dims) + [in_channels]):
+            raise NotImplementedError(f"ConvDecoder: widths {list(hidden_dims)} / slot dim {in_channels} "
+                                      f"(the variants take {K.SAVI_WIDTHS})")
         self.in_channels = self.in_features = in_channels
         self.hidden_dims, self.kernel_size = hidden_dims, kernel_size
         self.out_features, self.out_channels = hidden_dims[0], out_channels
-        self.upsample = None
+        self.upsample, self.batch_norm = upsample, batch_norm
         mods, c = [], in_channels
+        self._block_idx = []
         for i in range(len(hidden_dims) - 1, -1, -1):
-            mods.append(ConvBlock(c, hidden_dims[i], kernel_size, padding=kernel_size // 2))
+            self._block_idx.append(len(mods))
+            mods.append(ConvBlock(c, hidden_dims[i], kernel_size, padding=kernel_size // 2, batch_norm=batch_norm))
             c = hidden_dims[i]
+            if upsample is not None and i > 0:            # reference key layout: parameter-free entries in between
+                mods.append(Upsample(scale_factor=upsample))
+        self._tail_idx = len(mods)
         mods.append(nn.Conv2d(self.out_features, out_channels, kernel_size=3, stride=1, padding=1))
         self.decoder = nn.Sequential(*mods)
         self._derived = Derived()
@@ -90,6 +112,8 @@ class ConvDecoder(nn.Module):
         # the 64 -> 64 layers as vertical Winograd F(4, 5) x five horizontal taps (csrc/conv_wino.hip): 2.5 x fewer
         # matrix products in the same split-fp16 arithmetic, same error class (scripts/probes/winograd_numerics.py)
         self.conv_wino = os.environ.get("TOCVP_CONV_WINO", "1") != "0"
+        # arithmetic of the generic path's convs: f16x3 or fp32 (bf16x3 -> fp32, f16f8 -> f16x3: KNOBS.md)
+        self.generic_precision = {"bf16x3": "fp32", "f16f8": "f16x3"}.get(self.conv_precision, self.conv_precision)
 
     # -- derived weights -----------------------------------------------------------------------
     def _packed(self, i):
@@ -136,12 +160,90 @@ class ConvDecoder(nn.Module):
             return cpos, ts.reshape(25 * ts.shape[1], ts.shape[2])
         return self._derived.get("layer0", [c0.weight, c0.bias, pos_table], build)
 
-    range_fallbacks = {"conv_precision": {"f16x3": "bf16x3", "f16f8": "bf16x3"}}
+    range_fallbacks = {"conv_precision": {"f16x3": "bf16x3", "f16f8": "bf16x3"},
+                       "generic_precision": {"f16x3": "fp32"}}
 
     # -- forward -------------------------------------------------------------------------------
+    def output_size(self, resolution):
+        """ (H, W) of the decoded images for a broadcast ``resolution`` """
+        s = 2 ** (len(self.hidden_dims) - 1) if self.upsample else 1
+        return resolution[0] * s, resolution[1] * s
+
     def decode_slots(self, slots, pos_table, out=None):
+        if self.generic:
+            with K.range_owner(self, "generic_precision"):
+                return self._decode_generic(slots, pos_table, out=out)
         with K.range_owner(self, "conv_precision"):
             return self._decode_slots(slots, pos_table, out=out)
+
+    # -- generic path (variants) ---------------------------------------------------------------
+    def _block_params(self, j):
+        """ hidden block j (0 = the one fed by the broadcast): (block, [tensors its derived weights depend on]) """
+        blk = self.decoder[self._block_idx[j]]
+        deps = [blk.conv.weight, blk.conv.bias]
+        if self.batch_norm:
+            bn = blk.block[1]
+            deps += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        return blk, deps
+
+    def _scale_shift(self, j):
+        blk, deps = self._block_params(j)
+        return self._derived.get(f"gss{j}", deps, blk.folded_scale_shift)
+
+    def _generic_weights(self, j, precision):
+        """ packed weights of hidden block j >= 1 for kernels.convk: phase form for f16x3 after an upsampling """
+        blk, _ = self._block_params(j)
+        w = blk.conv.weight
+        if self.upsample and precision == "f16x3":
+            return self._derived.get(f"gwu{j}", [w], lambda: K.pack_conv_up2_weights(w))
+        return self._derived.get(f"gw{j}", [w], lambda: K.pack_conv_weights(w))
+
+    def _generic_layer0(self, pos_table):
+        """ (cpos (H, W, C0) = conv0(pos) without bias, tapsum (k k C0, D)) of the collapsed layer 0 """
+        c0 = self.decoder[self._block_idx[0]].conv
+        k = self.kernel_size
+
+        def build():
+            zero = torch.zeros(c0.weight.shape[0], device=c0.weight.device, dtype=torch.float32)
+            cpos = K.convk(pos_table[None].contiguous(), K.pack_conv_weights(c0.weight), None, zero, k, relu=False,
+                           precision="fp32")[0].contiguous()
+            ts = K.dec_tapsum_k(c0.weight)
+            return cpos, ts.reshape(k * k * ts.shape[1], ts.shape[2])
+        return self._derived.get("glayer0", [c0.weight, pos_table], build)
+
+    def _decode_generic(self, slots, pos_table, out=None):
+        """ slots (F, K, D), pos_table (H0, W0, D) -> recons_imgs (F,3,H,W), recons (F,K,3,H,W), masks (F,K,1,H,W) at
+        the output size; ``out`` as for _decode_slots """
+        F_, Ks, D = slots.shape
+        H0, W0, _ = pos_table.shape
+        H, W = self.output_size((H0, W0))
+        k, prec = self.kernel_size, self.generic_precision
+        cpos, tapsum = self._generic_layer0(pos_table)
+        C0 = cpos.shape[-1]
+        dev = slots.device
+        if out is not None:
+            imgs, recons, masks = out[:3]
+            clamped = out[3] if len(out) > 3 else None
+        else:
+            imgs = torch.empty((F_, 3, H, W), device=dev, dtype=torch.float32)
+            recons = torch.empty((F_, Ks, 3, H, W), device=dev, dtype=torch.float32)
+            masks = torch.empty((F_, Ks, 1, H, W), device=dev, dtype=torch.float32)
+            clamped = None
+        tail = self.decoder[self._tail_idx]
+        fpc = max(1, self.max_slot_images // Ks)
+        for f0 in range(0, F_, fpc):
+            f1 = min(F_, f0 + fpc)
+            n = (f1 - f0) * Ks
+            S = K.linear(slots[f0:f1].reshape(n, D), tapsum).reshape(n, k * k, C0)
+            sc, sh = self._scale_shift(0)
+            x = K.dec_layer0_expand(cpos, S, sc, sh, k, relu=True)
+            for j in range(1, len(self.hidden_dims)):
+                sc, sh = self._scale_shift(j)
+                x = K.convk(x, self._generic_weights(j, prec), sc, sh, k, relu=True, upsample2=bool(self.upsample),
+                            precision=prec)
+            dst = (imgs[f0:f1], recons[f0:f1], masks[f0:f1]) + ((clamped[f0:f1],) if clamped is not None else ())
+            K.dec_tail(x, tail.weight, tail.bias, f1 - f0, Ks, out=dst)
+        return imgs, recons, masks
 
     def _decode_slots(self, slots, pos_table, out=None):
         """

@@ -35,13 +35,19 @@ class SimpleConvEncoder(nn.Module):
     """
     Stack of Conv5x5 + ReLU at full resolution.  forward() takes the reference's NCHW input and
     returns NCHW for API parity; the model uses ``forward_nhwc`` which keeps activations NHWC
-    (channel-contiguous = coalesced for the implicit-GEMM kernel).
+    (channel-contiguous = coalesced for the implicit-GEMM kernel).  Kernel 3 / 7 (the reference's
+    ``kernel_size``) runs on kernels.convk_in3 / convk with widths 32 / 64 / 128.
     """
 
     def __init__(self, in_channels=3, hidden_dims=(64, 64, 64, 64), kernel_size=5, **kwargs):
         super().__init__()
-        if kernel_size != 5 or kwargs.get("downsample_encoder", False) or kwargs.get("batch_norm"):
-            raise NotImplementedError("SimpleConvEncoder: kernel 5, no downsampling / batch-norm")
+        if kernel_size not in (3, 5, 7) or kwargs.get("downsample_encoder", False) or kwargs.get("batch_norm"):
+            raise NotImplementedError("SimpleConvEncoder: kernel 3 / 5 / 7, no downsampling / batch-norm")
+        if kwargs.get("stride", 1) != 1 or kwargs.get("max_pool"):
+            raise NotImplementedError("SimpleConvEncoder: no stride / max-pool")
+        if kernel_size != 5 and any(h not in K.SAVI_WIDTHS for h in hidden_dims):
+            raise NotImplementedError(f"SimpleConvEncoder: widths {list(hidden_dims)} (kernel {kernel_size} takes "
+                                      f"{K.SAVI_WIDTHS})")
         if in_channels != 3:
             raise NotImplementedError("SimpleConvEncoder: RGB input only")
         self.in_channels, self.hidden_dims, self.kernel_size = in_channels, hidden_dims, kernel_size
@@ -59,6 +65,8 @@ class SimpleConvEncoder(nn.Module):
 
     def forward_nhwc(self, x):
         """ x: (n, 3, H, W) view of contiguous image planes -> (n, H, W, C) """
+        if self.kernel_size != 5:
+            return self._forward_nhwc_k(x)
         first = self.encoder[0].conv
         y = K.conv5x5_in3(x, first.weight, first.bias)
         with K.range_owner(self, "conv_precision"):
@@ -66,6 +74,18 @@ class SimpleConvEncoder(nn.Module):
                 conv = self.encoder[i].conv
                 wp = self._derived.get(f"wp{i}", [conv.weight], lambda c=conv: K.pack_conv_weights(c.weight))
                 y = K.conv5x5(y, wp, conv.bias, relu=True, precision=self.conv_precision)
+        return y
+
+    def _forward_nhwc_k(self, x):
+        """ kernel 3 / 7: first layer reads the NCHW images in place, the others run kernels.convk """
+        first = self.encoder[0].conv
+        y = K.convk_in3(x, first.weight, first.bias)
+        with K.range_owner(self, "conv_precision"):
+            prec = "fp32" if self.conv_precision == "fp32" else "f16x3"
+            for i in range(1, len(self.encoder)):
+                conv = self.encoder[i].conv
+                wp = self._derived.get(f"wp{i}", [conv.weight], lambda c=conv: K.pack_conv_weights(c.weight))
+                y = K.convk(y, wp, None, conv.bias, self.kernel_size, relu=True, precision=prec)
         return y
 
     def forward(self, x):

@@ -162,6 +162,22 @@ def fill_module_(module, seed=0, prefix="", family="damped"):
     return module
 
 
+@torch.no_grad()
+def fill_batchnorm_stats_(module, seed=0, prefix=""):
+    """
+    Non-trivial BatchNorm running statistics keyed by state_dict name: running_mean ~ N(0, 0.2), running_var ~ U(0.5, 2)
+    (fill_module_ gives every 1-d tensor 1 + U(+-0.2), under which folding the statistics into the conv would hardly be
+    tested).  Same values on the reference modules and on this package's mirrors.
+    """
+    for name, t in module.state_dict().items():
+        if name.endswith("running_mean"):
+            t.copy_(torch.from_numpy(synth_array(prefix + name, tuple(t.shape), "normal", 0.2, seed)).to(t.dtype))
+        elif name.endswith("running_var"):
+            u = synth_array(prefix + name, tuple(t.shape), "uniform", 0.75, seed)        # U(-0.75, 0.75)
+            t.copy_(torch.from_numpy(1.25 + u).to(t.dtype))
+    return module
+
+
 def synth_videos(batch, num_frames, channels=3, height=64, width=64, seed=0):
     """ videos in [0, 1], shape (B, L, C, H, W) """
     return synth_tensor("inputs.videos", (batch, num_frames, channels, height, width),

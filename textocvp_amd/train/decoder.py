@@ -45,6 +45,12 @@ class DecoderLoss:
         dec = savi.decoder
         if type(dec).__name__ != "ConvDecoder" or len(dec.hidden_dims) != 4:
             raise NotImplementedError("training step: SAVi ConvDecoder with 4 conv blocks (reference config)")
+        opts = [name for name, on in (("kernel_size=%d" % dec.kernel_size, dec.kernel_size != 5),
+                                      ("upsample=%s" % dec.upsample, dec.upsample is not None),
+                                      ("batch_norm", dec.batch_norm)) if on]
+        if opts:
+            raise NotImplementedError("training step: the decoder backward covers kernel 5 without upsampling or "
+                                      "batch-norm; this ConvDecoder has " + ", ".join(opts))
         self.savi, self.dec = savi, dec
         self.frames_per_chunk = frames_per_chunk
 

@@ -708,6 +708,25 @@ int tocvp_slot_composite_bwd_f32(const float* dR, const float* decoded, const fl
                                  int K, int N, int F, int ld, void* stream);
 int tocvp_ln_bcast_bwd_f32(const float* slots, const float* pos, const float* gamma, const float* dy, float* dslot,
                            int S, int N, int D, float eps, void* stream);
+/* Frozen SAVi decoder variants (generic ConvDecoder path: kernel 3 / 5 / 7, nearest x2 upsampling, eval BatchNorm,
+ * widths 32 / 64 / 128), backward w.r.t. the slots (csrc/convk_bwd.hip):
+ *  tocvp_convk_dgrad_bf16x3_f32: dx (nimg,H,W,Cout) = gate' * data gradient of a ksize x ksize conv (pad ksize/2) over g
+ *    (nimg,H,W,Cg), or with up2 of "nearest x2 -> ksize x ksize conv" over g (nimg,2H,2W,Cg): a stride-2 (ksize+1)^2-tap
+ *    correlation, tap (ty,tx) reading g[2y + ty - ksize/2][2x + tx - ksize/2] (the adjoint of tocvp_convk_f16x3_f32's
+ *    phase convolutions).  Plain taps read g[y + ty - ksize/2][x + tx - ksize/2].  wsplit = bf16 planes (2 = hi | lo,
+ *    taps, Cout, Cg) of the transposed, flipped (or phase-summed) weights, BatchNorm scale folded (kernels.
+ *    pack_convk_dgrad_weights).  gate (nimg,H,W,Cout) may be NULL (else dx = 0 where gate <= 0).  Cg, Cout in
+ *    {32, 64, 128}, ksize in {3, 5, 7}, any H, W.  bf16x3 split operands, fp32 accumulation, no atomics.
+ *  tocvp_conv3x3_t4w_f32: tocvp_conv3x3_t4_f32 for C in {32, 64, 128} and any W.
+ *  tocvp_dec_class_reduce_k_f32: dS (nimg, ksize^2, C) = scale[c] * sum over the pixels of each border class (the map of
+ *    tocvp_dec_layer0_expand_f32) of g (nimg,H,W,C) * ((cpos + S[cls]) * scale + shift > 0); scale may be NULL (= 1).
+ *    H, W >= ksize, C in {32, 64, 128}. */
+int tocvp_convk_dgrad_bf16x3_f32(const float* g, const void* wsplit, const float* gate, float* dx, int nimg, int H,
+                                 int W, int Cg, int Cout, int ksize, int up2, void* stream);
+int tocvp_conv3x3_t4w_f32(const float* dy, const float* w, const float* act, float* dx, int nimg, int H, int W, int C,
+                          void* stream);
+int tocvp_dec_class_reduce_k_f32(const float* g, const float* cpos, const float* S, const float* scale, const float* shift,
+                                 float* dS, int nimg, int H, int W, int C, int ksize, void* stream);
 /* torch.optim.Adam step (no weight decay / amsgrad) on a flat parameter.  The step-dependent scalars are
  * read from DEVICE memory so that a captured HIP graph of the training step can be replayed:
  * hyper = {lr, beta1, beta2, eps, 1 - beta1^t, 1 - beta2^t}; gscale (may be NULL) = clipping factor.

@@ -7,12 +7,18 @@ frozen decomp -> BPTT rollout -> frozen decoder forward/backward -> clipped Adam
   --model dinosaur  ExtendedDINOSAUR (ViT-B/14 backbone, MLPPatchDecoder + CNN image head, --img-size) + TextOCVP_T5;
                     defaults batch 32, 24 slots.  Also reports the eager split of one step: decomp, rollout BPTT
                     (+ slot loss, clipping, Adam) and the patch decoder's loss + backward.
+  --savi-variant    a SAVi variant (up2, k3, bn_up2_128, k7_mixed) built from the committed
+                    tests/golden/state_dict_manifest_savi_<tag>.json, at its own image size.  Also reports the eager split
+                    of one step: decomp, rollout BPTT (+ slot loss, clipping, Adam), the generic decoder's loss +
+                    backward, and the forward decode of the same frames.
 One process per GPU; with torchrun the gradients are averaged by one flat all-reduce per step.
 
     python scripts/bench_train.py [--model savi] [--batch 64] [--slots 8] [--preds 9] [--steps 5] [--warmup 2]
     python scripts/bench_train.py --model dinosaur [--img-size 224] [--batch 32] [--slots 24]
+    python scripts/bench_train.py --savi-variant up2 [--batch 64] [--slots 8]
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -21,7 +27,8 @@ import time
 import torch
 import torch.distributed as dist
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
 from textocvp_amd import synth                                                        # noqa: E402
 from textocvp_amd.setup_model import (default_dinosaur_params, default_exp_params, setup_model,   # noqa: E402
                                       setup_predictor)
@@ -47,8 +54,13 @@ def eager_split(ts, model, videos, tokens, lengths, noise, extra, a):
     slots = hist[:, nc:].reshape(a.batch * P, a.slots, -1).contiguous()
     tgt = videos[:, nc:nc + P].reshape(a.batch * P, *videos.shape[2:]).contiguous()
     dec = timed(lambda: ts.decoder.loss_and_slot_grad(slots, tgt, 2.0 / tgt.numel()))
-    return {"step": round(step, 1), "decomp": round(decomp, 1), "rollout_bptt_and_optimiser": round(step - decomp - dec, 1),
-            "patch_decoder_loss_and_backward": round(dec, 1),
+    out = {"step": round(step, 1), "decomp": round(decomp, 1), "rollout_bptt_and_optimiser": round(step - decomp - dec, 1)}
+    if a.savi_variant:
+        with torch.no_grad():
+            fwd = timed(lambda: model.decode(slots))
+        return {**out, "decoder_loss_and_backward": round(dec, 1), "decoder_forward_decode": round(fwd, 1),
+                "backward_over_forward": round(dec / fwd, 2), "decoder_frames_per_chunk": ts.decoder.chunk_frames(a.slots)}
+    return {**out, "patch_decoder_loss_and_backward": round(dec, 1),
             "patch_decoder_frames_per_chunk": ts.decoder.chunk_frames(a.slots)}
 
 
@@ -56,6 +68,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("savi", "dinosaur"), default="savi")
     ap.add_argument("--img-size", type=int, default=224, help="ExtendedDINOSAUR image size (multiple of 14)")
+    ap.add_argument("--savi-variant", choices=("up2", "k3", "bn_up2_128", "k7_mixed"), default=None,
+                    help="SAVi variant of tests/golden/state_dict_manifest_savi_<tag>.json (with --model savi)")
     ap.add_argument("--batch", type=int, default=None, help="default 64 (savi) / 32 (dinosaur)")
     ap.add_argument("--slots", type=int, default=None, help="default 8 (savi) / 24 (dinosaur)")
     ap.add_argument("--preds", type=int, default=9)
@@ -79,6 +93,16 @@ def main():
         savi = setup_model(default_dinosaur_params(num_slots=a.slots, img_size=a.img_size)).eval()
         synth.fill_module_(savi, prefix="dino.", family="undamped")
         res = a.img_size
+    elif a.savi_variant:
+        with open(os.path.join(ROOT, "tests", "golden", f"state_dict_manifest_savi_{a.savi_variant}.json")) as f:
+            model_params = copy.deepcopy(json.load(f)["model_params"])
+        model_params["num_slots"] = a.slots
+        exp = default_exp_params(num_slots=a.slots, num_context=1, num_preds=a.preds)
+        exp["model"]["model_params"] = model_params
+        savi = setup_model(exp["model"]).eval()
+        synth.fill_module_(savi, prefix="savi.")
+        synth.fill_batchnorm_stats_(savi, prefix="savi.")
+        res = model_params["encoder"]["encoder_params"]["resolution"][0]
     else:
         exp = default_exp_params(num_slots=a.slots, num_context=1, num_preds=a.preds)
         savi = setup_model(exp["model"]).eval()
@@ -111,7 +135,7 @@ def main():
         out = run(videos, tokens, lengths, init_noise=noise, **extra)
     fence()
     dt = time.perf_counter() - t0
-    split = eager_split(ts, savi, videos, tokens, lengths, noise, extra, a) if dino else None
+    split = eager_split(ts, savi, videos, tokens, lengths, noise, extra, a) if dino or a.savi_variant else None
     if rank == 0:
         print(json.dumps({
             "metric": "predictor training steps/s", "value": round(a.steps / dt, 3), "unit": "steps/s",
@@ -119,7 +143,8 @@ def main():
             "launch_mode": "eager" if a.eager else "hip graphs (fwd+bwd, optimiser)",
             "sequences_per_s": round(world * a.batch * a.steps / dt, 1),
             "config": {"workload": ("TextOCVP_T5 training step, frozen ExtendedDINOSAUR" if dino else
-                                    "configs[4]: TextOCVP_CustomTF training step, frozen SAVi") +
+                                    f"TextOCVP_CustomTF training step, frozen SAVi variant {a.savi_variant}"
+                                    if a.savi_variant else "configs[4]: TextOCVP_CustomTF training step, frozen SAVi") +
                                    ", image + slot MSE, clipped Adam", "batch_per_gpu": a.batch, "num_slots": a.slots,
                        "num_preds": a.preds, "resolution": res},
             **({"eager_split_ms": split} if split else {}),

@@ -266,6 +266,17 @@ _SIGNATURES = {
     "tocvp_conv3x3_dgrad_bf16x3_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_convk_dgrad_bf16x3_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p]),
+    "tocvp_conv3x3_t4w_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p]),
+    "tocvp_dec_class_reduce_k_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_void_p]),
     "tocvp_bilinear_resize_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_int, ctypes.c_void_p]),
@@ -1823,6 +1834,95 @@ def dec_layer0_expand(cpos, S, scale, shift, ksize, relu=True):
     _check(lib().tocvp_dec_layer0_expand_f32(_ptr(cpos), _ptr(S), _ptr(scale), _ptr(shift), _ptr(y), n, H, W, C, ksize,
                                              int(bool(relu)), _stream()), "tocvp_dec_layer0_expand_f32")
     return y
+
+
+# ---- backward of the SAVi decoder variants (training step, csrc/convk_bwd.hip) -----------------------------------------
+def _up2_dgrad_rows(k):
+    """ (k + 1, k) 0/1 matrix: tap t of an axis of the up2 data gradient (high-resolution offset t - k // 2 from 2 y) sums
+    the forward taps d = a + 2 (k // 2) - t, a in {0, 1} (the two high-resolution pixels that duplicate source pixel y) """
+    r = k // 2
+    m = torch.zeros((k + 1, k), dtype=torch.float64)
+    for t in range(k + 1):
+        for a in range(2):
+            d = a + 2 * r - t
+            if 0 <= d < k:
+                m[t, d] = 1.0
+    return m
+
+
+def convk_dgrad_weights64(weight, scale=None, up2=False):
+    """
+    (Cout, Cin, k, k) forward weights (x per-Cout BatchNorm scale) -> (taps, Cin, Cout) float64 data-gradient weights of
+    convk_dgrad: plain, tap (ty, tx) = W[:, :, k-1-ty, k-1-tx]^T (transposed, flipped; k^2 taps); up2, (k + 1)^2 taps of the
+    stride-2 correlation, tap (ty, tx) = sum of the forward taps of _up2_dgrad_rows (phase-summed).  k = 3 with up2 gives
+    the 16 taps of conv3x3_dgrad.
+    """
+    k = int(weight.shape[-1])
+    assert k % 2 == 1 and weight.shape[-2] == k
+    Cout, Cin = weight.shape[:2]
+    w = weight.detach().double()
+    if scale is not None:
+        w = w * scale.detach().double()[:, None, None, None]
+    if not up2:
+        return w.flip(-1, -2).permute(2, 3, 1, 0).reshape(k * k, Cin, Cout)
+    m = _up2_dgrad_rows(k).to(w.device)
+    return torch.einsum("ta,sb,oiab->tsio", m, m, w).reshape((k + 1) ** 2, Cin, Cout)
+
+
+def pack_convk_dgrad_weights(weight, scale=None, up2=False):
+    """ convk_dgrad_weights64 rounded once to fp32 and split into the kernel's bf16 planes: (2 = hi | lo, taps, Cin, Cout) """
+    wd = convk_dgrad_weights64(weight, scale, up2).float()
+    hi = wd.to(torch.bfloat16)
+    lo = (wd - hi.float()).to(torch.bfloat16)
+    return torch.stack((hi, lo)).contiguous()
+
+
+def convk_dgrad(g, wsplit, out_hw, ksize, gate=None, up2=False):
+    """
+    Data gradient of a ksize x ksize conv (pad ksize // 2) -- or of "nearest x2 -> ksize x ksize conv" (up2) -- over the
+    gradient image g (n, GH, GW, Cg) NHWC -> dx (n, H, W, Cout), (GH, GW) = (H, W) or (2 H, 2 W); wsplit from
+    pack_convk_dgrad_weights; ``gate`` (n, H, W, Cout): dx is zeroed where gate <= 0.  bf16x3 split operands.
+    """
+    n, GH, GW, Cg = g.shape
+    H, W = out_hw
+    nt = ksize + 1 if up2 else ksize
+    Cout = wsplit.shape[2]
+    if Cg not in SAVI_WIDTHS or Cout not in SAVI_WIDTHS or ksize not in (3, 5, 7):
+        raise NotImplementedError(f"convk_dgrad: widths {Cg} -> {Cout}, kernel {ksize}")
+    assert g.is_contiguous() and wsplit.is_contiguous() and wsplit.dtype == torch.bfloat16
+    assert tuple(wsplit.shape) == (2, nt * nt, Cout, Cg), (tuple(wsplit.shape), nt, Cg)
+    assert (GH, GW) == ((2 * H, 2 * W) if up2 else (H, W))
+    assert gate is None or (gate.is_contiguous() and tuple(gate.shape) == (n, H, W, Cout))
+    dx = torch.empty((n, H, W, Cout), device=g.device, dtype=torch.float32)
+    _timed(lambda: f"convk{ksize}_dgrad{'_up2' if up2 else ''}_{n}x{H}x{W}x{Cg}x{Cout}",
+           2.0 * n * H * W * nt * nt * Cg * Cout, lambda: _check(
+               lib().tocvp_convk_dgrad_bf16x3_f32(_ptr(g), _ptr(wsplit), _ptr(gate), _ptr(dx), n, H, W, Cg, Cout, ksize,
+                                                  int(bool(up2)), _stream()), "tocvp_convk_dgrad_bf16x3_f32"))
+    return dx
+
+
+def conv3x3_t4w(dy, w, act):
+    """ tail backward: dy (n, H, W, 4), w (4, C, 3, 3) tail weight, act (n, H, W, C) the last hidden activation ->
+    relu'(act) * conv_transpose3x3(dy) (n, H, W, C), C in {32, 64, 128} """
+    n, H, W, C = act.shape
+    assert dy.is_contiguous() and act.is_contiguous() and tuple(dy.shape) == (n, H, W, 4)
+    assert tuple(w.shape) == (4, C, 3, 3)
+    dx = torch.empty_like(act)
+    _check(lib().tocvp_conv3x3_t4w_f32(_ptr(dy), _ptr(w.contiguous()), _ptr(act), _ptr(dx), n, H, W, C, _stream()),
+           "tocvp_conv3x3_t4w_f32")
+    return dx
+
+
+def dec_class_reduce_k(g, cpos, S, scale, shift, ksize):
+    """ backward of dec_layer0_expand (relu=True) w.r.t. S: g (n, H, W, C) = gradient of layer 0's output -> dS (n, k^2, C)
+    = scale * per-border-class sums of g where (cpos + S[cls]) * scale + shift > 0 """
+    n, H, W, C = g.shape
+    assert g.is_contiguous() and cpos.is_contiguous() and S.is_contiguous()
+    assert tuple(cpos.shape) == (H, W, C) and tuple(S.shape) == (n, ksize * ksize, C)
+    dS = torch.empty((n, ksize * ksize, C), device=g.device, dtype=torch.float32)
+    _check(lib().tocvp_dec_class_reduce_k_f32(_ptr(g), _ptr(cpos), _ptr(S), _ptr(scale), _ptr(shift), _ptr(dS), n, H, W,
+                                              C, ksize, _stream()), "tocvp_dec_class_reduce_k_f32")
+    return dS
 
 
 def slot_composite(decoded, feat_dim=None):

@@ -4,7 +4,7 @@ One optimisation step of the TextOCVP predictor (reference 04_train_predictor.py
   slot_history = SAVi.decomp(videos)                      (frozen, no gradient; SAVi or ExtendedDINOSAUR)
   pred_slots   = autoregressive rollout                    (TrainablePredictor, BPTT)
   pred_imgs    = SAVi.decode(pred_slots)                   (frozen decoder, gradient w.r.t. the slots:
-                                                            DecoderLoss / PatchDecoderLoss)
+                                                            DecoderLoss / GenericDecoderLoss / PatchDecoderLoss)
   loss = w_img * MSE(pred_imgs, target_imgs) + w_slot * MSE(pred_slots, target_slots)   (CONFIG.py:42-51)
   clip_grad_norm_(0.05) -> Adam(lr 1e-4) with linear warm-up + cosine annealing (lib/setup_model.py:285-332)
 
@@ -21,6 +21,7 @@ import torch.distributed as dist
 from .. import kernels as K
 from . import autograd as ag
 from .decoder import DecoderLoss
+from .decoder_generic import GenericDecoderLoss
 from .patch_decoder import PatchDecoderLoss
 from .predictor import TrainablePredictor
 
@@ -31,6 +32,16 @@ _L = K.lib
 
 def _s():
     return torch.cuda.current_stream().cuda_stream
+
+
+def decoder_loss(savi):
+    """ the image-loss term of the frozen model's decoder: SAVi's ConvDecoder in the shipped configuration (DecoderLoss) or
+    a variant on its generic path (GenericDecoderLoss), or ExtendedDINOSAUR's MLPPatchDecoder (PatchDecoderLoss) """
+    if type(savi.decoder).__name__ == "MLPPatchDecoder":
+        return PatchDecoderLoss(savi)
+    if getattr(savi.decoder, "generic", False):
+        return GenericDecoderLoss(savi)
+    return DecoderLoss(savi)
 
 
 class StepResult(Mapping):
@@ -70,11 +81,7 @@ class PredictorTrainStep:
                  process_group=None, text_dropout=None, generator=None):
         self.savi, self.wrapper = savi.eval(), wrapper
         self.model = TrainablePredictor(wrapper, text_dropout=text_dropout, generator=generator)
-        # the frozen model's decoder: SAVi's ConvDecoder or ExtendedDINOSAUR's MLPPatchDecoder
-        if type(savi.decoder).__name__ == "MLPPatchDecoder":
-            self.decoder = PatchDecoderLoss(savi)
-        else:
-            self.decoder = DecoderLoss(savi)
+        self.decoder = decoder_loss(savi)
         self.lr, self.betas, self.eps, self.clip = lr, betas, eps, clip
         self.w_img, self.w_slot = loss_weights
         self.warmup_steps, self.scheduler_steps, self.eta_min = warmup_steps, scheduler_steps, eta_min

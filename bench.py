@@ -7,8 +7,14 @@ One "step" = one pass of the hot path over one batch of synthetic sequences:
 at BASELINE.json configs[1]: 30 slots, 64x64x3, 1 seed + 19 predicted frames.  Inputs and weights
 are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-extra]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extra] [--no-legs]]
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the outputs of the last of
+them if --dump-outputs is given, and the result line (metric, value, unit, ms_per_step, dtype, mean PSNR / SSIM).
+Everything else the benchmark measures runs only with --full, after the headline's timed steps: the second timed region
+(value_no_overlap, roofline), the per-kernel pass (rooflines), "extra" and the CPU baseline; --no-extra, --no-legs and
+--no-cpu-baseline leave parts of it out.
 
 --dump-outputs DIR: after the K timed steps of the reported value, rank 0 writes what the LAST of them computed -- every
 tensor forward_eval returns, and the PSNR / SSIM rows of the metric step -- as DIR/<name>.npy (dump_outputs: at most
@@ -21,7 +27,7 @@ waits for them -- it replaces the reference's nn.DataParallel wrap (base/baseEva
 Every rank runs its own batches (weak scaling, no collective inside the rollout); the per-sequence
 PSNR / SSIM rows are all-gathered ONCE at the end (RCCL).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0; with --full it also carries
   "roofline":     dominant kernel (decoder 5x5 conv) timed IN the timed region with HIP events,
   "rooflines":    that entry + predictor GEMM, predictor attention and the slot-attention iteration
                   (HBM-bound, GB/s), each timed with HIP events in one extra untimed pass,
@@ -85,10 +91,13 @@ def parse():
                     help="strong scaling: --batch is the GLOBAL batch, split evenly over the ranks (the semantics of the "
                          "reference's nn.DataParallel, base/baseEvaluator.py:142-145, which scatters ONE batch over its "
                          "devices); default: weak scaling, --batch sequences per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the batch-32 / 8 / 1 lines, the per-kernel pass and the "
-                                                           "config-4 / training legs")
-    ap.add_argument("--no-legs", action="store_true", help="skip only the config-4 and training legs of `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure value_no_overlap and the rooflines, the other "
+                         "batches, captions and configs of `extra` and the CPU baseline (default: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the batch-32 / 8 / 1 lines, the per-kernel "
+                                                           "pass and the config-4 / training legs")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the config-4 and training legs of `extra`")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step as DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
@@ -615,7 +624,7 @@ def main():
     if rank == 0:
         log(f"world={world} batch/gpu={B} warmup={args.warmup} steps={args.steps}")
     # region 1 (the reported value): decoder overlapped with the rollout on a second HIP stream, no events.
-    # region 2 (value_no_overlap + the dominant kernel's roofline): the same K steps, serial order, HIP events
+    # region 2 (--full: value_no_overlap + the dominant kernel's roofline): the same K steps, serial order, HIP events
     # around the decoder convolutions only -- a kernel's duration is its own when nothing shares the chip.
     elapsed, _, all_metrics = timed(inp, args.warmup, args.steps, timer_only=(), overlap_decode=True)
     if last is not None:
@@ -623,23 +632,25 @@ def main():
             shapes = dump_outputs(args.dump_outputs, last)
             log(f"outputs of the last timed step -> {args.dump_outputs}: {shapes}")
         last = None
-    clock = ClockSampler(getattr(torch.cuda.get_device_properties(dev), "pci_bus_id", None)) if rank == 0 else None
-    if clock is not None:
-        clock.start()
-    elapsed_no, timer, _ = timed(inp, 0, args.steps, overlap_decode=False)
-    sclk = clock.stop() if clock is not None else None
+    elapsed_no, timer, sclk = None, None, None
+    if args.full:
+        clock = ClockSampler(getattr(torch.cuda.get_device_properties(dev), "pci_bus_id", None)) if rank == 0 else None
+        if clock is not None:
+            clock.start()
+        elapsed_no, timer, _ = timed(inp, 0, args.steps, overlap_decode=False)
+        sclk = clock.stop() if clock is not None else None
 
     # Outside the timed region (rank 0): one pass with the decoder NOT overlapped with the rollout and EVERY
     # instrumented kernel bracketed by HIP events (thousands of event pairs would perturb the timed region).
     timer_all = None
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and args.full and not args.no_extra:
         kernels.TIMER = kernels.LaunchTimer(only=("conv5x5", "gemm_", "mlp_fused_", "mha_", "slot_attn_"))
         step(inp, overlap_decode=False)
         torch.cuda.synchronize()
         timer_all, kernels.TIMER = kernels.TIMER, None
 
     extra = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         extra = {}
         notes = {32: "the authors' evaluation batch (scripts/05_evaluate_TextOCVP_CATER.sh)",
                  8: "small evaluation batch", 1: "one sequence: ms_per_step is the latency of 1 seed + 19 predicted "
@@ -708,7 +719,7 @@ def main():
         kernel_name, units, peak = CONV_MODES.get(cp, CONV_MODES["fp32"])
         rooflines = []
         roofline = None
-        conv = timer.summary().get("conv5x5_64_64")
+        conv = timer.summary().get("conv5x5_64_64") if timer is not None else None
         if conv and conv["launches"]:
             avg_ms = conv["total_ms"] / conv["launches"]
             gflop_per_launch = CONV_GFLOP_PER_SLOT_IMAGE * conv["units"] / conv["launches"]
@@ -827,8 +838,6 @@ def main():
             "value": round(frames / elapsed, 2), "unit": "predicted frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 2),
-            "value_no_overlap": round(frames / elapsed_no, 2),
-            "ms_per_step_no_overlap": round(1e3 * elapsed_no / args.steps, 2),
             "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None,
             "dtype": arithmetic_string(savi, pred, kernels),
             "data": "synthetic",
@@ -841,11 +850,14 @@ def main():
             "path_tflops": round(frames * PATH_GFLOP_PER_FRAME / 1e3 / elapsed, 2),
             "mean_psnr": round(float(m[0].item()), 3), "mean_ssim": round(float(m[1].item()), 4),
             "gathered_rows": int(all_metrics.shape[0]),
-            "roofline": roofline, "rooflines": rooflines,
         }
+        if args.full:
+            line.update({"value_no_overlap": round(frames / elapsed_no, 2),
+                         "ms_per_step_no_overlap": round(1e3 * elapsed_no / args.steps, 2),
+                         "roofline": roofline, "rooflines": rooflines})
         if extra:
             line["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             log(f"GPU: {line['value']} frames/s; timing the CPU oracle (warm-up + 5 reps of 2 sequences) ...")
             line["cpu_baseline"] = cpu_baseline(savi, pred)
         print(json.dumps(line), flush=True)

@@ -122,6 +122,18 @@ def test_bench_launcher_argument_to_children_env():
     assert started == []
 
 
+def test_bench_full_is_opt_in(monkeypatch):
+    """ a plain run measures the headline alone; everything else the benchmark measures waits for --full """
+    import sys
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert not args.full and not args.no_extra and not args.no_legs and not args.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-legs"])
+    args = bench.parse()
+    assert args.full and args.no_legs and not args.no_extra
+
+
 def _run_launcher(extra_env, *argv, timeout=300):
     import subprocess
     import sys

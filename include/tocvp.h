@@ -571,11 +571,33 @@ int tocvp_bilinear_resize_f32(const float* x, float* y, int n, int C, int cstrid
  *   psnr[n] = 10 log10(1 / (mse_n + 1e-8)),   ssim[n] = mean SSIM map (11-tap Gaussian sigma 1.5,
  *   valid padding, k1 0.01, k2 0.03, channel average).  preds/targets: (N, C, H, W) fp32;
  *   clamp01 != 0 clamps both to [0,1] on load (the evaluator's clamp, 05_evaluate_predictor.py:96-99).
- *   psnr or ssim may be NULL.  ws: tocvp_metrics_ws_bytes(N, C) bytes.  H*W*8 <= 160 KiB.
+ *   psnr or ssim may be NULL.  H, W >= 11, W <= 1861.  ws: tocvp_metrics_ws_bytes_hw(N, C, H, W) bytes
+ *   (= tocvp_metrics_ws_bytes(N, C) for frames with H*W*8 <= 160 KiB - 64; larger frames run the banded
+ *   form, one workgroup per (image, channel, band of output rows)).
  * ------------------------------------------------------------------------------------------- */
 size_t tocvp_metrics_ws_bytes(int N, int C);
+size_t tocvp_metrics_ws_bytes_hw(int N, int C, int H, int W);
 int tocvp_psnr_ssim_f32(const float* preds, const float* targets, float* psnr, float* ssim, int N,
                         int C, int H, int W, int clamp01, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * LPIPS (reference lib/metrics.py:259-298: piqa 1.2.2 LPIPS(network="alex"), definition restated in
+ * csrc/lpips.hip): out[n] = LPIPS(clamp01(preds[n]), clamp01(targets[n])), preds/targets (N, 3, H, W)
+ * fp32 NCHW read in place, H, W >= 31, N <= 65535.  wpk: tocvp_lpips_weights_floats() floats, the
+ * packed AlexNet features + lin weights (layout in csrc/lpips.hip), 16-byte aligned.
+ * ws: tocvp_lpips_ws_bytes(N, H, W) bytes, 16-byte aligned (the five taps of all 2N images; the
+ * caller chunks over images to bound it).
+ * tocvp_lpips_conv_f32: layer l in [0, 5) alone, bias + ReLU, NHWC out.  l = 0: x / x2 are NCHW frames
+ * (images < nfirst from x, the rest from x2), clamped and scaled on load; l > 0: x NHWC (nimg, H, W, Cin).
+ * tocvp_lpips_maxpool_f32: max-pool 3 / 2 NHWC, C % 4 == 0.
+ * ------------------------------------------------------------------------------------------- */
+size_t tocvp_lpips_weights_floats(void);
+size_t tocvp_lpips_ws_bytes(int N, int H, int W);
+int tocvp_lpips_f32(const float* preds, const float* targets, const float* wpk, float* out, int N, int H,
+                    int W, void* ws, size_t ws_bytes, void* stream);
+int tocvp_lpips_conv_f32(int layer, const float* x, const float* x2, int nfirst, const float* wpk, float* y,
+                         int nimg, int H, int W, void* stream);
+int tocvp_lpips_maxpool_f32(const float* x, float* y, int nimg, int H, int W, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Text cross-attention of one predictor block, collapsed over the caption (csrc/xattn.hip):

@@ -290,6 +290,17 @@ _SIGNATURES = {
                                       ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tocvp_clip_scale_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     "tocvp_metrics_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "tocvp_metrics_ws_bytes_hw": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "tocvp_lpips_weights_floats": (ctypes.c_size_t, []),
+    "tocvp_lpips_ws_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "tocvp_lpips_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "tocvp_lpips_conv_f32": (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "tocvp_lpips_maxpool_f32": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "tocvp_psnr_ssim_f32": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
@@ -1660,13 +1671,98 @@ def psnr_ssim(preds, targets, clamp01=True, want_psnr=True, want_ssim=True):
     assert preds.shape == targets.shape and preds.dim() == 4
     preds, targets = preds.contiguous(), targets.contiguous()
     N, C, H, W = preds.shape
-    ws = torch.empty(max(1, N * C * 2), device=preds.device, dtype=torch.float32)
+    ws_bytes = lib().tocvp_metrics_ws_bytes_hw(N, C, H, W)    # larger than N C 2 floats for the banded form
+    ws = torch.empty(max(1, N * C * 2, (ws_bytes + 3) // 4), device=preds.device, dtype=torch.float32)
     psnr = torch.empty(N, device=preds.device, dtype=torch.float32) if want_psnr else None
     ssim = torch.empty(N, device=preds.device, dtype=torch.float32) if want_ssim else None
     _check(lib().tocvp_psnr_ssim_f32(_ptr(preds), _ptr(targets), _ptr(psnr), _ptr(ssim), N, C, H, W,
                                      int(bool(clamp01)), _ptr(ws), ws.numel() * 4, _stream()),
            "tocvp_psnr_ssim_f32")
     return psnr, ssim
+
+
+# --------------------------------------------------------------------------------------------
+# LPIPS (csrc/lpips.hip): AlexNet features on exact fp32 MFMA + the lin head
+# --------------------------------------------------------------------------------------------
+LPIPS_LAYERS = ((11, 3, 64), (5, 64, 192), (3, 192, 384), (3, 384, 256), (3, 256, 256))   # (kernel, Cin, Cout)
+LPIPS_WS_LIMIT = 1 << 30
+
+
+def pack_lpips_weights(conv_w, conv_b, lin, device):
+    """ five AlexNet conv weights (Cout, Cin, k, k) / biases (Cout,) and five lin vectors (C,) -> the packed fp32 device
+    buffer of csrc/lpips.hip: per layer W[k][co] with k = (ky k + kx) Cin + ci, rows zero-padded to a multiple of 32, then
+    the bias; the lin vectors last """
+    parts = []
+    for (ks, cin, cout), w, b in zip(LPIPS_LAYERS, conv_w, conv_b):
+        K = ks * ks * cin
+        m = torch.zeros((K + 31) // 32 * 32, cout, dtype=torch.float32)
+        m[:K] = w.detach().to(torch.float32).cpu().permute(2, 3, 1, 0).reshape(K, cout)
+        parts += [m.reshape(-1), b.detach().to(torch.float32).cpu().reshape(-1)]
+    parts += [v.detach().to(torch.float32).cpu().reshape(-1) for v in lin]
+    flat = torch.cat(parts)
+    if flat.numel() != lib().tocvp_lpips_weights_floats():
+        raise TocvpError(f"packed LPIPS weights hold {flat.numel()} floats, the kernel expects "
+                         f"{lib().tocvp_lpips_weights_floats()}")
+    return flat.to(device)
+
+
+def lpips_ws_bytes(N, H, W):
+    return lib().tocvp_lpips_ws_bytes(N, H, W)
+
+
+def lpips(preds, targets, packed, max_ws_bytes=LPIPS_WS_LIMIT):
+    """ preds, targets (N, 3, H, W) fp32 on device (clamped to [0, 1] inside) -> (N,) LPIPS.  Chunks over image pairs so
+    that the workspace (the five AlexNet taps of both images of every pair in a chunk) stays within max_ws_bytes. """
+    _dev_f32(preds, "preds"), _dev_f32(targets, "targets"), _dev_f32(packed, "packed LPIPS weights")
+    if preds.shape != targets.shape or preds.dim() != 4 or preds.shape[1] != 3:
+        raise ValueError(f"LPIPS takes two (N, 3, H, W) tensors, got {tuple(preds.shape)} and {tuple(targets.shape)}")
+    N, _, H, W = preds.shape
+    if H < 31 or W < 31:
+        raise ValueError(f"LPIPS needs H, W >= 31 (the second AlexNet pool is empty below), got {H}x{W}")
+    preds, targets = preds.contiguous(), targets.contiguous()
+    out = torch.empty(N, device=preds.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    chunk = max(1, min(N, 65535, max_ws_bytes // lpips_ws_bytes(1, H, W)))
+    while chunk > 1 and lpips_ws_bytes(chunk, H, W) > max_ws_bytes:
+        chunk -= 1
+    nbytes = lpips_ws_bytes(min(chunk, N), H, W)
+    ws = torch.empty((nbytes + 3) // 4, device=preds.device, dtype=torch.float32)
+    st = _stream()
+    for n0 in range(0, N, chunk):
+        n = min(chunk, N - n0)
+        _check(lib().tocvp_lpips_f32(_ptr(preds[n0:n0 + n]), _ptr(targets[n0:n0 + n]), _ptr(packed), _ptr(out[n0:n0 + n]),
+                                     n, H, W, _ptr(ws), nbytes, st), "tocvp_lpips_f32")
+    return out
+
+
+def lpips_conv(layer, x, packed, x2=None):
+    """ one AlexNet layer of the LPIPS kernel alone (bias + ReLU): layer 0 takes (n, 3, H, W) NCHW frames (clamped and
+    scaled inside; x2 appended as further images), later layers (n, H, W, Cin) NHWC.  -> (n, OH, OW, Cout) NHWC """
+    ks, cin, cout = LPIPS_LAYERS[layer]
+    stride, pad = (4, 2) if layer == 0 else (1, ks // 2)
+    _dev_f32(x, "x"), _dev_f32(packed, "packed LPIPS weights")
+    x = x.contiguous()
+    if layer == 0:
+        x2 = x2.contiguous() if x2 is not None else None
+        nfirst, nimg, H, W = x.shape[0], x.shape[0] + (x2.shape[0] if x2 is not None else 0), x.shape[2], x.shape[3]
+    else:
+        nfirst, (nimg, H, W, _) = 0, x.shape
+    OH, OW = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    y = torch.empty(nimg, OH, OW, cout, device=x.device, dtype=torch.float32)
+    _check(lib().tocvp_lpips_conv_f32(layer, _ptr(x), _ptr(x2), nfirst, _ptr(packed), _ptr(y), nimg, H, W, _stream()),
+           "tocvp_lpips_conv_f32")
+    return y
+
+
+def lpips_maxpool(x):
+    """ (n, H, W, C) NHWC -> max-pool 3 / 2 (n, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C) """
+    _dev_f32(x, "x")
+    x = x.contiguous()
+    n, H, W, C = x.shape
+    y = torch.empty(n, (H - 3) // 2 + 1, (W - 3) // 2 + 1, C, device=x.device, dtype=torch.float32)
+    _check(lib().tocvp_lpips_maxpool_f32(_ptr(x), _ptr(y), n, H, W, C, _stream()), "tocvp_lpips_maxpool_f32")
+    return y
 
 
 def conv3x3(x, wp, scale, shift, relu=True, upsample2=False, precision="fp32"):

@@ -14,6 +14,14 @@
 //    planes, product = Xl Yh + Xh Yl + Xh Yh, fp32 accumulate: fp32-class, ~2^-21 per product): the exact
 //    fp32 MFMA (64 cycles per K = 2) made this kernel matrix-bound at ~1.8 TB/s, the split form needs
 //    5.3x fewer matrix cycles and leaves HBM as the limit.  Valid for |q*scale|, |k|, |v| < 255;
+//  * the attention weights are split at a PER-SLOT power of two, 2^(8 - ex) with ex the binary exponent of the slot's
+//    running maximum over the wave's tiles (not at the fixed 2^8 of q / k / v): the weights are normalised over the
+//    locations, and a slot that wins no location has all of them near eps = 1e-8, whose fixed-scale planes
+//    (2.6e-6) were fp16 subnormals with ~6 significant bits -- the slot's update came out scaled by 1 +- 1e-3 while
+//    the fp32 row sum was exact.  Now every slot's largest weight sits in [2^7, 2^8); weights below 2^-22 of it
+//    (below eps for a slot whose maximum is ~1) still drop out of the numerator.  A grown exponent rescales that
+//    slot's accumulators by the exact power of two (one ballot per tile skips it when no slot grew), and the scale
+//    is undone before the 4-wave reduction: records, ticket and the fixed-order sum are as before;
 //  * dots = q k^T is computed with the SLOTS ON THE ACCUMULATOR REGISTERS (rows) and the locations on
 //    the lanes: the softmax over slots is 15 in-lane max / add steps plus ONE cross-half exchange per
 //    tile (slots on lanes cost ten 32-lane butterflies per register);
@@ -57,6 +65,8 @@ constexpr int CNT_BYTES = 1024;               // ticket words in front of the re
 constexpr float SA = TOCVP_F16X3_ACT_SCALE;   // 2^8
 constexpr float F16MAX = 65504.f;
 constexpr float NEG_BIG = -1.0e30f;
+constexpr int EX_BIAS = 160;                  // exponent bias of the per-slot scales: a stored 0 (-160) is below every weight's
+                                              // exponent (fp32 denormals end at 2^-149), the largest (1 + eps: 1) fits a byte
 
 struct SaArgs {
     const float* q; const float* k; const float* v; int ldkv;   // PLANES: k = the plane rows, v unused, ldkv = 256
@@ -79,6 +89,31 @@ __device__ __forceinline__ void split4(const f32x4 v, f16x4& hi, f16x4& lo) {
         hi[u] = (_Float16)X;
         lo[u] = (_Float16)(X - (float)hi[u]);
     }
+}
+
+// four attention weights -> fp16 planes of 2^e x, e per weight (the slot's exponent: v_ldexp_f32 is exact)
+__device__ __forceinline__ void split4_exp(const f32x4 v, const int (&e)[4], f16x4& hi, f16x4& lo) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float X = clampf(__builtin_amdgcn_ldexpf(v[u], e[u]), F16MAX);
+        hi[u] = (_Float16)X;
+        lo[u] = (_Float16)(X - (float)hi[u]);
+    }
+}
+
+// max over the 32 lanes of one wave half of a value >= 0: four DPP steps inside each 16-lane row, then the two rows of
+// the half swap through ds_swizzle (bitmask mode, xor 16) -- no LDS traffic, lanes l and l ^ 32 stay separate
+template <int CTRL>
+__device__ __forceinline__ float max_dpp(float v) {
+    const int o = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false);
+    return fmaxf(v, __builtin_bit_cast(float, o));
+}
+__device__ __forceinline__ float half_max32_nonneg(float v) {
+    v = max_dpp<0xB1>(v);            // quad_perm [1, 0, 3, 2]
+    v = max_dpp<0x4E>(v);            // quad_perm [2, 3, 0, 1]
+    v = max_dpp<0x141>(v);           // row_half_mirror
+    v = max_dpp<0x140>(v);           // row_mirror
+    return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F)));
 }
 
 // MFMA 32x32x16 operand fragment (8 consecutive k for this lane's row / column) out of a ROW-MAJOR
@@ -167,6 +202,12 @@ __global__ __launch_bounds__(256, 1) void slot_attn_kernel(SaArgs p) {
     float rs[16];                   // per-lane partial row sums: slot acc_row(r, h), this lane's location column
 #pragma unroll
     for (int r = 0; r < 16; ++r) rs[r] = 0.f;
+    // binary exponent ex of the running maximum of slot acc_row(r, h)'s weights over the wave's tiles (uniform over the
+    // lane half), kept as byte j of exb[g4] (r = 4 g4 + j) biased by EX_BIAS: the slot's weights enter the matrix cores as
+    // planes of 2^(8 - ex) x, so that its largest weight sits in [2^7, 2^8) whatever its size, and u[.][r] holds
+    // 2^(16 - ex) * the slot's partial update
+    unsigned exb[4] = {0u, 0u, 0u, 0u};
+    auto exp_of = [&](int r) { return (int)__builtin_amdgcn_ubfe(exb[r >> 2], 8 * (r & 3), 8) - EX_BIAS; };
 
     // lane-constant LDS addresses
     const int w_off_k = h * KROW + l31 * 8;                       // staging write, k image (+ 2 it rows)
@@ -257,13 +298,46 @@ __global__ __launch_bounds__(256, 1) void slot_attn_kernel(SaArgs p) {
                 if (acc_row(r, h) < p.Ks) ao[(size_t)acc_row(r, h) * p.N] = x[r];
         }
 
-        // ---- d. attn planes -> LDS image [location l31][slot], over the k image (its reads are complete: the
-        //         wave's LDS operations execute in order): registers 4 g .. 4 g + 3 = slots 8 g + 4 h ..
+        // ---- d0. per-slot scale of the weights.  Slot attention normalises over LOCATIONS: a slot that wins no
+        //          location has all its weights near eps, and at the fixed scale 2^8 of the other operands they would
+        //          fall among the fp16 subnormals (2^8 eps = 2.6e-6: ~6 significant bits, every weight of the slot
+        //          rounded the same way while the row sum rs is fp32).  The scale follows the slot's running maximum;
+        //          when its exponent grows, the slot's accumulators are rescaled by the exact power of two (skipped
+        //          by a ballot when no slot of the wave grew: after the first tiles, almost always)
+        {
+            bool grew = false;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4)
+                if (8 * g4 < p.Ks)                                // wave-uniform: register groups that hold a slot
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        grew |= x[4 * g4 + j] >= __builtin_amdgcn_ldexpf(1.f, exp_of(4 * g4 + j));   // max >= 2^ex
+            if (__builtin_amdgcn_ballot_w64(grew) != 0) {         // rare after the first tile: the slots' maxima
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    if (8 * g4 >= p.Ks) continue;
+                    unsigned nb = 0u;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int r = 4 * g4 + j, e0 = exp_of(r);
+                        const int e = max(e0, __builtin_amdgcn_frexp_expf(half_max32_nonneg(x[r])));
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) u[n][r] = __builtin_amdgcn_ldexpf(u[n][r], e0 - e);
+                        nb |= (unsigned)(e + EX_BIAS) << (8 * j);
+                    }
+                    exb[g4] = nb;
+                }
+            }
+        }
+
+        // ---- d. attn planes (2^(8 - ex) x) -> LDS image [location l31][slot], over the k image (its reads are
+        //         complete: the wave's LDS operations execute in order): registers 4 g .. 4 g + 3 = slots 8 g + 4 h ..
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f16x4 hi, lo;
-            split4(f32x4{x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3]}, hi, lo);
+            const int es[4] = {8 - exp_of(4 * g4), 8 - exp_of(4 * g4 + 1), 8 - exp_of(4 * g4 + 2), 8 - exp_of(4 * g4 + 3)};
+            split4_exp(f32x4{x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3]}, es, hi, lo);
             unsigned char* dst = wl + l31 * AROW + (8 * g4 + 4 * h) * 2;
             *reinterpret_cast<f16x4*>(dst) = hi;
             *reinterpret_cast<f16x4*>(dst + APLANE) = lo;
@@ -295,7 +369,7 @@ __global__ __launch_bounds__(256, 1) void slot_attn_kernel(SaArgs p) {
     for (int n = 0; n < 4; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            red[(wave * 32 + acc_row(r, h)) * SD + 32 * n + l31] = u[n][r] * INV;
+            red[(wave * 32 + acc_row(r, h)) * SD + 32 * n + l31] = __builtin_amdgcn_ldexpf(u[n][r], exp_of(r) - 16);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const float tot = half_sum32(rs[r]);
